@@ -19,6 +19,12 @@ over the same data as every other N.
 `roofline.kernel_ms` is the device time of the scan kernels of one step, taken with HIP events recorded on the
 stream the kernels run on (ph_exec_stats.device_ms); `traffic` is read from the PMC summary under profiles/
 (tools/gpu_pmc.sh) when one exists for the workload.
+
+A plain run sets up, warms up, times `--steps` steps and prints the result line.  `--full` adds what takes runs of its
+own after the timed steps: the CPU baseline (the oracle over a sample of the same segments, `cpu_baseline`) and the
+bit-exact comparison of the GPU's result with the oracle's on that sample (`parity_sample`); `--no-cpu` and
+`--no-parity` drop either from a `--full` run.  `--dump-outputs DIR` writes the result columns of the last timed step
+as DIR/<name>.npy (dump_outputs).
 """
 import argparse
 import json
@@ -159,6 +165,44 @@ def oracle_segments(bufs):
                                            for c, cb in b.columns.items()}) for b in bufs]
 
 
+DUMP_LIMIT_BYTES = 60_000_000  # --dump-outputs writes at most 64 MB; the margin covers headers and one-row results
+
+
+def dump_column(col):
+    """One result column as float32 / float64 without loss: int32, int64 (COUNT: < 2^53) and float64 columns as
+    float64, float32 and uint8 (HLL registers, [groups, m]) as float32, string keys as the [groups, width] matrix of
+    their NUL-padded UTF-8 bytes in float32."""
+    if not isinstance(col, np.ndarray):
+        enc = [s.encode("utf-8") for s in col]
+        width = max([len(e) for e in enc] + [1])
+        return np.frombuffer(b"".join(e.ljust(width, b"\0") for e in enc), np.uint8).reshape(len(enc), width) \
+            .astype(np.float32)
+    return col.astype(np.float32 if col.dtype in (np.uint8, np.float32) else np.float64)
+
+
+def dump_outputs(directory, results, suffix=""):
+    """--dump-outputs: the columns a caller of the timed path received in the last timed step -- per group-by column
+    `<prefix>key<i>`, per aggregation `<prefix>agg<k>`, rows in the order the library returned them -- as
+    <directory>/<name><suffix>.npy.  results: [(prefix, IntermediateResult)].  Above DUMP_LIMIT_BYTES in all, every
+    result keeps the same fixed, seeded sample of its rows (one index set per result, ascending)."""
+    os.makedirs(directory, exist_ok=True)
+    named = []
+    for prefix, r in results:
+        cols = [(f"{prefix}key{g}", c) for g, c in enumerate(r.key_columns)]
+        cols += [(f"{prefix}agg{k}", c) for k, c in enumerate(r.agg_columns)]
+        named.append([(name, dump_column(c)) for name, c in cols])
+    total = sum(a.nbytes for cols in named for _, a in cols)
+    for cols in named:
+        rows = len(cols[0][1]) if cols else 0
+        keep = None
+        if total > DUMP_LIMIT_BYTES and rows > 1:
+            k = max(1, int(rows * (DUMP_LIMIT_BYTES / total)))
+            keep = np.sort(np.random.default_rng([0xD0, rows]).choice(rows, k, replace=False))
+        for name, a in cols:
+            np.save(os.path.join(directory, f"{name}{suffix}.npy"), a if keep is None else a[keep])
+    log(f"wrote {sum(len(c) for c in named)} arrays to {directory}")
+
+
 def query_columns(q):
     cols = list(q.group_by)
     for a in q.aggregations:
@@ -201,14 +245,20 @@ def flight_main(args, world, rank, dist, device):
     alg = sum(sum((seg_rows * any_buf.columns[c].bits + 7) // 8 for c in query_columns(q)) * len(mine)
               for q in queries)
 
+    last = []  # --dump-outputs: the step's results, one per query
+
     def step():
         ms = 0.0
+        del last[:]
         for q in queries:
             if world > 1:
-                _, _, scan = runner.execute(q, pinned, copy=False)
+                res, _, scan = runner.execute(q, pinned, copy=False)
                 ms += scan.device_ms
             else:
-                ms += ctx.execute(q, pinned, copy=False).stats.device_ms
+                res = ctx.execute(q, pinned, copy=False)
+                ms += res.stats.device_ms
+            if args.dump_outputs:
+                last.append(res)  # None: a rank whose key shard is empty
         return ms
     for _ in range(args.warmup):
         step()
@@ -257,7 +307,11 @@ def flight_main(args, world, rank, dist, device):
                      "kernel_ms": kernel_ms,
                      "algorithmic_bytes_per_launch": alg},
     }
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, [(f"q{i:02d}_", r) for i, r in enumerate(last) if r is not None],
+                     f"_rank{rank}" if world > 1 else "")
+    del last[:]
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:
         threads = host_threads()
         osegs = oracle_segments([built[0]])
         t1 = time.perf_counter()
@@ -353,8 +407,12 @@ def main():
                                                            "config1 1e7")
     ap.add_argument("--segment-rows", type=int, default=None, help="default 1e7")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU-baseline sample size in seconds of work")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-parity", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the CPU baseline and the parity check against the oracle")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: no CPU baseline (and no parity check)")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: no parity check")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the result columns of the last timed step as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--workload", default="config3", choices=sorted(list(WORKLOADS) + list(BUILT) + list(FLIGHTS)))
     ap.add_argument("--devices", default=None,
                     help="comma-separated HIP ordinals: ONE process drives one multi-device context over them "
@@ -528,7 +586,9 @@ def main():
     if devices:
         result["n_gpus"] = len(set(devices))
         result["devices"] = devices
-    if rank == 0 and world == 1 and not args.no_cpu and not devices:
+    if args.dump_outputs and last.get("res") is not None:
+        dump_outputs(args.dump_outputs, [("", last["res"])], f"_rank{rank}" if world > 1 else "")
+    if rank == 0 and world == 1 and args.full and not args.no_cpu and not devices:
         threads = host_threads()
         log(f"[rank {rank}] {ms_per_step:.3f} ms/step; CPU baseline on {threads} threads")
         n, dt, dt1, keys, aggs = cpu_baseline(bufs, q, threads, args.cpu_seconds, ora_makers or None)

@@ -17,7 +17,7 @@ case ${PHASE:-tests} in
     rc=$?; echo "smoke rc=$rc"; tail -3 gpurun_out/r4f_smoke.log; exit $rc ;;
   bench)
     for w in ${BENCH:-config3 config2 config3-agg config3-lds config1}; do
-      timeout -k 10 ${BTIME:-400} python -u bench.py --workload $w --steps ${STEPS:-10} --warmup 3 --cpu-seconds ${CPU_SECS:-10} \
+      timeout -k 10 ${BTIME:-400} python -u bench.py --full --workload $w --steps ${STEPS:-10} --warmup 3 --cpu-seconds ${CPU_SECS:-10} \
         > gpurun_out/r4f_bench_$w.json 2> gpurun_out/r4f_bench_$w.err
       rc=$?; echo "bench $w rc=$rc"; cat gpurun_out/r4f_bench_$w.json
       [ $rc -eq 0 ] || { tail -20 gpurun_out/r4f_bench_$w.err; exit $rc; }
