@@ -322,8 +322,10 @@ int32_t ph_segment_device(const ph_segment* seg);  /* index into the context's d
  * AggregationPlanNode.java:122-141 choose it: StarTreeFilterOperator's traversal on the host
  * (StarTreeFilterOperator.java:207-358) gives the star-tree documents, the remaining predicates and the
  * aggregation over the pair columns run in the same kernels as any query (COUNT sums count__*, SUM / MIN / MAX read
- * sum__ / min__ / max__).  A pair of another function (e.g. distinctCountHLL__c) is recorded: a query it would serve
- * is PH_ERR_UNSUPPORTED (CPU plan). */
+ * sum__ / min__ / max__).  A distinctCountHLL__c pair (BYTES: one serialized HyperLogLog per record, a var-byte raw
+ * forward index) is validated at pin and its records' registers pinned as a sketch column: DISTINCTCOUNTHLL(c) of the
+ * pair's log2m merges the matched records' registers on the GPU (another log2m is PH_ERR_UNSUPPORTED: CPU plan).  A
+ * pair of any other function is recorded: a query it would serve is PH_ERR_UNSUPPORTED (CPU plan). */
 typedef struct {
   const void* tree;             /* the STAR_TREE buffer (OffHeapStarTree.java:45-83 format, little-endian) */
   uint64_t tree_size;
@@ -334,14 +336,21 @@ typedef struct {
   const uint64_t* dimension_forward_index_size;
   int32_t num_metrics;          /* startree.v2.<i>.function.column.pairs ("count__*", "sum__col", ...) */
   const char* const* metrics;
-  const void* const* metric_forward_index;     /* <pair>.FORWARD_INDEX raw forward index (LONG count, DOUBLE others);
-                                                  NULL for a pair of another function */
+  const void* const* metric_forward_index;     /* <pair>.FORWARD_INDEX raw forward index (LONG count, DOUBLE sum / min /
+                                                  max, var-byte BYTES distinctCountHLL); NULL for a pair of another
+                                                  function */
   const uint64_t* metric_forward_index_size;
 } ph_star_tree_desc;
 int ph_segment_add_star_tree(ph_segment* seg, const ph_star_tree_desc* desc);
 int32_t ph_segment_num_star_trees(const ph_segment* seg);
 /* Host-only parse of a STAR_TREE buffer (OffHeapStarTree's checks: magic, version, header size, node count). */
 int ph_star_tree_check(const void* tree, uint64_t tree_size, int32_t* num_nodes, int32_t* num_dimensions);
+/* Host-only parse of a distinctCountHLL__<col> pair's forward index, exactly the validation ph_segment_add_star_tree
+ * runs: a var-byte chunk forward index (VarByteChunkForwardIndexWriter versions 2 and 3, any codec of the raw forward
+ * indexes) of num_docs serialized HyperLogLogs (int32 BE log2m, int32 BE register bytes, RegisterSet words), every
+ * offset inside its chunk and the buffer, every record of one log2m in 1..16 and of the length that log2m gives.
+ * *log2m receives it.  A malformed buffer is PH_ERR_INVALID_ARGUMENT, never an over-read. */
+int ph_star_tree_hll_pair_check(const void* buf, uint64_t size, int32_t num_docs, int32_t* log2m);
 
 /* Table-level sorted value union for a column (group keys share ids across segments and GPUs).
  * Optional: without it the union of the queried segments' dictionaries is used. */

@@ -124,6 +124,7 @@ void star_tree_forget(Context& c, ph_segment* seg) {
 }
 void star_tree_add_impl(ph_segment* seg, const ph_star_tree_desc* d);
 void star_tree_check_impl(const void* tree, uint64_t size, int32_t* num_nodes, int32_t* num_dimensions);
+void star_tree_hll_pair_check_impl(const void* buf, uint64_t size, int32_t num_docs, int32_t* log2m);
 }  // namespace ph
 
 extern "C" {
@@ -233,6 +234,10 @@ int32_t ph_segment_num_star_trees(const ph_segment* seg) { return seg ? (int32_t
 
 int ph_star_tree_check(const void* tree, uint64_t tree_size, int32_t* num_nodes, int32_t* num_dimensions) {
   return guarded([&] { ph::star_tree_check_impl(tree, tree_size, num_nodes, num_dimensions); });
+}
+
+int ph_star_tree_hll_pair_check(const void* buf, uint64_t size, int32_t num_docs, int32_t* log2m) {
+  return guarded([&] { ph::star_tree_hll_pair_check_impl(buf, size, num_docs, log2m); });
 }
 
 int64_t ph_segment_device_bytes(const ph_segment* seg) {

@@ -29,6 +29,10 @@ void launch_scan(const KParams& p, int mode, int ng, int rec64, int grid, size_t
     return;
   }
   PH_HIP_CHECK(hipGetLastError());  // a failure left by an earlier unchecked call is reported as such, not as ours
+  if (p.sk_list) {  // DISTINCTCOUNTHLL over star-tree sketch columns: the scan's sketch variant + the register merge
+    launch_scan_sketch(p, mode, ng, grid, lds, s);
+    return;
+  }
   switch (mode) {
     case MODE_COUNT:
     case MODE_AGG: launch_scan_agg(p, mode, grid, lds, s); break;

@@ -17,6 +17,7 @@
 #include <exception>
 #include <cstdint>
 #include <deque>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -65,6 +66,11 @@ struct DevColumn {
   const uint32_t* hll;   // dictId -> (register index << 8) | rank   (DISTINCTCOUNTHLL)
   int32_t bits;
   int32_t cardinality;
+  // a star-tree view's sketch column (distinctCountHLL__<col>): [num_docs][sketch_words] native-endian RegisterSet
+  // words of each record's HyperLogLog (six 5-bit registers per word), read by k_hll_sketch_merge; nullptr otherwise
+  const uint32_t* sketch;
+  int32_t sketch_words;
+  int32_t pad;
 };
 
 enum : int32_t {
@@ -211,6 +217,9 @@ struct DevSegment {
   // ph_filter_execute (KParams::docset): the segment's doc bitmap, ceil(num_docs / 64) 64-bit words (bit i of word w =
   // doc 64 w + i), written by the MODE_COUNT scans; words outside the scanned chunks stay as zeroed by the host
   uint32_t* docset;
+  // sketch queries (KParams::sk_list): this segment's first document in the launch's match list numbering
+  uint32_t sk_doc_base;
+  int32_t pad3;
   DevColumn cols[kMaxCols];
   DevValCol vals[kMaxVals];
   DevValCol vals2[kMaxVals];       // second operand of a 2-operand expression term (KParams::val_op)
@@ -337,6 +346,14 @@ struct KParams {
   int64_t* ovf_sum;
   int64_t* ovf_min;
   int64_t* ovf_max;
+  // DISTINCTCOUNTHLL over star-tree sketch columns (scan_hll_sketch.hip).  HLL slot h with hll_words[h] != 0 reads a
+  // sketch column: the scan appends (row base in out_hll, launch-wide document) per matched record to sk_list and
+  // k_hll_sketch_merge, right after the scan on the same stream, merges the records' registers into out_hll.
+  int32_t hll_words[kMaxHll];     // RegisterSet words per record of slot h's sketch column (0: per-dictId table)
+  int32_t num_segs;               // device segments of the launch (the merge finds a list entry's segment)
+  uint32_t sk_cap;                // entries sk_list holds
+  unsigned long long* sk_list;    // [sk_cap] (document << 32 | row base); nullptr: no sketch slot
+  uint32_t* sk_count;             // entries appended by the scan (zeroed again by the merge's launch)
 };
 
 // Kernel B of the partitioned group-by: aggregates one batch of records per partition in LDS, then merges
@@ -536,6 +553,11 @@ struct Column {
   DeviceBuffer d_fwd;
   DeviceBuffer d_values;
   DeviceBuffer d_inverted;
+  // a star-tree view's distinctCountHLL__<col> pair (startree.cpp): no forward index or dictionary, but every record's
+  // serialized HyperLogLog as sketch_words native-endian RegisterSet words, [num_docs][sketch_words] in HBM
+  DeviceBuffer d_sketch;
+  int32_t sketch_words = 0;
+  int32_t sketch_log2m = 0;
   std::mutex cache_mu;
   std::map<int, HllTable> hll_tables;                                // by log2m
   bool vpacked_ready = false;                                        // VK_PACKED stream built
@@ -613,13 +635,14 @@ struct ph_segment {
 namespace ph {
 // A star-tree of a pinned segment (StarTreeV2): the tree on the host (OffHeapStarTree nodes, 7 ints each: dimension,
 // value, start, end, aggregated doc, first child, last child) and its records pinned as a segment of their own -- the
-// split-order dimensions with the segment's dictionaries, the count / sum / min / max pair columns as raw columns
+// split-order dimensions with the segment's dictionaries, the count / sum / min / max pair columns as raw columns, a
+// distinctCountHLL pair as a sketch column (Column::d_sketch)
 struct StarTree {
   std::vector<std::string> dims;
   std::vector<int32_t> nodes;
   int32_t num_nodes = 0;
   std::vector<std::string> pairs;     // every function-column pair of the tree
-  std::set<std::string> served;       // the pairs pinned in `view` (count / sum / min / max)
+  std::set<std::string> served;       // the pairs pinned in `view` (count / sum / min / max / distinctCountHLL)
   ph_segment* view = nullptr;         // owned
   ~StarTree();
 };
@@ -761,6 +784,9 @@ void launch_reduce_table(void* dst, const void* src, int64_t n, int32_t op, hipS
 void launch_fill_identity(void* dst, int64_t n, int32_t op, hipStream_t s);                 // op's identity
 enum : int32_t { PH_HLL_HASH_INT = 0, PH_HLL_HASH_DOUBLE = 1, PH_HLL_HASH_FLOAT = 2 };
 void launch_hll_table(const void* values, int32_t kind, int64_t n, int log2m, uint32_t* out, hipStream_t s);
+// scan_hll_sketch.hip: the generic scan's sketch variant (a launch whose KParams::sk_list is set) followed by
+// k_hll_sketch_merge over the list it appended
+void launch_scan_sketch(const KParams& p, int mode, int ng, int grid, size_t lds, hipStream_t s);
 
 void build_bitmap_directory(Column& c);  // at pin, from c.inverted
 // at pin: the (key, slice) container directory of an exact range index's RangeBitmap (after Pinot's 12-byte header)
@@ -884,6 +910,14 @@ void fixed_bit_pack_host(const int32_t* ids, int64_t n, int bits, uint8_t* out);
 // raw (no-dictionary) forward indexes (rawfwd.cpp): decode a chunk forward index to native values, and
 // dictionary-encode native values (sorted distinct values + per-doc ids)
 void raw_forward_index_decode(const uint8_t* buf, uint64_t size, int32_t data_type, int64_t num_docs, void* out);
+// a var-byte chunk forward index (VarByteChunkForwardIndexWriter, versions 2 and 3): emit(doc, bytes, length) for the
+// docs [0, num_docs) in order; the bytes are valid during the call only
+void var_byte_forward_index_read(const uint8_t* buf, uint64_t size, int64_t num_docs,
+                                 const std::function<void(int64_t, const uint8_t*, size_t)>& emit);
+// a star-tree's distinctCountHLL__<col> pair column (BYTES: serialized HyperLogLogs of one log2m): validates every
+// record, returns log2m and, with `words`, the records' RegisterSet words in native endian ([num_docs][m / 6 + 1])
+void hll_pair_column_parse(const uint8_t* buf, uint64_t size, int64_t num_docs, const std::string& pair, int32_t* log2m,
+                           std::vector<uint32_t>* words);
 std::vector<uint8_t> result_to_datatable(const ph_result* r, const ph_query* q, const ph_metadata_entry* extra,
                                          int32_t num_extra);
 void raw_dictionary_encode(int32_t data_type, const void* values, int64_t n, Dictionary* dict, std::vector<int32_t>* ids);

@@ -1271,6 +1271,35 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
       auto it = s->columns.find(c);
       if (it == s->columns.end()) fail(PH_ERR_BAD_QUERY, "Column not found: " + c + " in segment " + s->name);
     }
+  // DISTINCTCOUNTHLL slots that read a star-tree view's sketch column (startree.cpp rewrites the aggregation onto
+  // distinctCountHLL__<col>): the records' RegisterSet words per slot, the same in every segment of the call
+  std::vector<int32_t> hll_words(hll_cols.size(), 0);
+  bool any_sketch = false;
+  for (auto* s : segs)
+    for (auto& c : slot_names) {
+      const Column& col = *s->columns.at(c);
+      if (!col.sketch_words) continue;
+      const auto it = std::find(hll_cols.begin(), hll_cols.end(), c);
+      const bool other_use = std::find(group_cols.begin(), group_cols.end(), c) != group_cols.end() ||
+                             std::find(val_cols.begin(), val_cols.end(), c) != val_cols.end() ||
+                             std::find(val_cols2.begin(), val_cols2.end(), c) != val_cols2.end();
+      if (it == hll_cols.end() || other_use || !star) fail(PH_ERR_UNSUPPORTED, "sketch column " + c + " outside DISTINCTCOUNTHLL");
+      if (col.sketch_log2m != log2m) fail(PH_ERR_UNSUPPORTED, "sketch column " + c + " has another log2m");
+      hll_words[(size_t)(it - hll_cols.begin())] = col.sketch_words;
+      any_sketch = true;
+    }
+  if (any_sketch) {
+    if (q->filter_root >= 0)
+      for (int i = 0; i < q->num_predicates; ++i)
+        for (size_t h = 0; h < hll_cols.size(); ++h)
+          if (hll_words[h] && hll_cols[h] == q->predicates[i].column)
+            fail(PH_ERR_UNSUPPORTED, "predicate on a sketch column");
+    for (auto* s : segs)
+      for (size_t h = 0; h < hll_cols.size(); ++h)
+        if (s->columns.at(hll_cols[h])->sketch_words != hll_words[h])
+          fail(PH_ERR_UNSUPPORTED, "sketch column " + hll_cols[h] + " is not one in every segment");
+    if (dop) fail(PH_ERR_UNSUPPORTED, "sketch columns on dense partials");
+  }
   // |value| bound of term j over the queried segments (integer terms only; 0 when unknown)
   std::vector<double> term_amax(nvals, 0.0);
   for (int j = 0; j < nvals; ++j) {
@@ -1720,7 +1749,10 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
     kp.val_is_int[j] = val_is_int[j];
     kp.val_op[j] = val_exprs[j];
   }
-  for (int h = 0; h < num_hll; ++h) kp.hll_slot[h] = pl.slot.at(hll_cols[h]);
+  for (int h = 0; h < num_hll; ++h) {
+    kp.hll_slot[h] = pl.slot.at(hll_cols[h]);
+    kp.hll_words[h] = hll_words[h];
+  }
 
   // packed streams of the hot loop: slot 0 = the single-leaf filter column of each segment (if any),
   // then the group-by columns, then the aggregated value columns; all of them are LDS-staged.
@@ -1872,7 +1904,8 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
     size_t lds_table_max = 64 * 1024;
     if (ctx->has(OPT_LDS_TABLE_MAX)) lds_table_max = (size_t)std::max<int64_t>(0, ctx->opt(OPT_LDS_TABLE_MAX));
     const bool cache_ok = num_hll == 0 && nvals <= 1 && !ctx->has(OPT_NO_GROUP_CACHE);
-    if (off <= (cache_ok ? lds_table_max : (size_t)64 * 1024)) {
+    // (an explicit lds_table_max holds for every query: tests force the HBM table of a DISTINCTCOUNTHLL group-by)
+    if (off <= ((cache_ok || ctx->has(OPT_LDS_TABLE_MAX)) ? lds_table_max : (size_t)64 * 1024)) {
       mode = MODE_GROUP_LDS;
       lds_tables = off;
     } else if (part_ok && G >= 65536) {
@@ -1931,7 +1964,7 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
     return scratch.alloc<uint8_t>(bytes);
   };
   int tix = 0;
-  const int64_t hll_words = TR * num_hll * (m ? m : 1);
+  const int64_t hll_table_words = TR * num_hll * (m ? m : 1);
   kp.out_count = reinterpret_cast<unsigned long long*>(out_table(tix, 8 * (size_t)TR));
   for (int j = 0; j < nvals; ++j) {
     if (val_ops[j] & 1) kp.out_sum[j] = out_table(tix, 8 * (size_t)TR);
@@ -1942,7 +1975,7 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
     hkeys = scratch.alloc<unsigned long long>(TR);
     kp.hkeys = hkeys;
   }
-  if (num_hll) kp.out_hll = reinterpret_cast<uint32_t*>(out_table(tix, 4 * (size_t)hll_words));
+  if (num_hll) kp.out_hll = reinterpret_cast<uint32_t*>(out_table(tix, 4 * (size_t)hll_table_words));
   // identities of every output table (again before a numGroupsLimit rescan)
   auto init_tables = [&]() {
     PH_HIP_CHECK(hipMemsetAsync(kp.out_count, 0, sizeof(unsigned long long) * TR, st));
@@ -1952,7 +1985,7 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
       if (val_ops[j] & 4) launch_fill_i64(kp.out_max[j], INT64_MIN, TR, st);
     }
     if (hkeys) PH_HIP_CHECK(hipMemsetAsync(hkeys, 0xFF, 8 * TR, st));  // kHashEmpty
-    if (num_hll) PH_HIP_CHECK(hipMemsetAsync(kp.out_hll, 0, 4 * hll_words, st));
+    if (num_hll) PH_HIP_CHECK(hipMemsetAsync(kp.out_hll, 0, 4 * hll_table_words, st));
   };
   init_tables();
 
@@ -2026,6 +2059,7 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
     }
     agg_conj = ok && docs > 0 && hits * 8 < docs;
     if (ctx->has(OPT_AGG_SPARSE)) agg_conj = ok && docs > 0 && ctx->opt(OPT_AGG_SPARSE) != 0;
+    if (any_sketch) agg_conj = false;  // k_agg_sparse looks HLL entries up per dictId: sketch slots run the generic scan
   }
   std::vector<std::pair<int32_t, int32_t>> dseg_chunks;                // device segment -> its chunk range
   std::vector<int> dseg_src;                                           // device segment -> query segment index
@@ -2154,8 +2188,15 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
     }
     for (int g = 0; g < q->num_group_by; ++g)
       d.cols[kp.group_slot[g]].remap = segment_remap(ctx, *s, *s->columns.at(group_cols[g]), *gdicts[g]);
-    for (int h = 0; h < num_hll; ++h)
-      d.cols[kp.hll_slot[h]].hll = segment_hll_table(ctx, *s->columns.at(hll_cols[h]), log2m, st);
+    for (int h = 0; h < num_hll; ++h) {
+      Column& hc = *s->columns.at(hll_cols[h]);
+      if (hll_words[h]) {
+        d.cols[kp.hll_slot[h]].sketch = hc.d_sketch.as<uint32_t>();
+        d.cols[kp.hll_slot[h]].sketch_words = hc.sketch_words;
+      } else {
+        d.cols[kp.hll_slot[h]].hll = segment_hll_table(ctx, hc, log2m, st);
+      }
+    }
     for (int j = 0; j < nvals; ++j) {
       for (int o = 0; o < (val_exprs[j] ? 2 : 1); ++o) {
         Column& c = *s->columns.at(o ? val_cols2[j] : val_cols[j]);
@@ -2221,6 +2262,7 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
     }
     agg_sparse_plan = (all_bitmap_agg && hits * 8 < docs) || agg_conj;
     if (ctx->has(OPT_AGG_SPARSE)) agg_sparse_plan = (all_bitmap_agg || agg_conj) && ctx->opt(OPT_AGG_SPARSE) != 0;
+    if (any_sketch) agg_sparse_plan = false;
   }
   const bool agg_cont_plan = cont_defer && agg_sparse_plan && all_bitmap_agg && !agg_conj;
   int64_t chunk_docs_total = 0;  // the streaming chunk list's words x 64 and its widest chunk
@@ -2656,6 +2698,23 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
         off += ss.leaves.size() * nw;
       }
     }
+  }
+  // sketch slots: the launch's match list -- every document of every view x sketch slots, numbered over the device
+  // segments in order -- and its device-side entry count (scan_hll_sketch.hip)
+  if (any_sketch && !dsegs.empty()) {
+    uint64_t docs = 0, nsk = 0;
+    for (int h = 0; h < num_hll; ++h) nsk += hll_words[h] != 0;
+    for (auto& d : dsegs) {
+      d.sk_doc_base = (uint32_t)docs;
+      docs += (uint64_t)d.num_docs;
+    }
+    if (docs * nsk >= (1ull << 31) || (uint64_t)hll_table_words >= (1ull << 32))
+      fail(PH_ERR_UNSUPPORTED, "sketch columns: too many records or result registers for one launch");
+    kp.sk_cap = (uint32_t)std::max<uint64_t>(1, docs * nsk);
+    kp.sk_list = scratch.alloc<unsigned long long>(kp.sk_cap);
+    kp.sk_count = scratch.alloc<uint32_t>(1);
+    kp.num_segs = (int32_t)dsegs.size();
+    PH_HIP_CHECK(hipMemsetAsync(kp.sk_count, 0, sizeof(uint32_t), st));
   }
   // the optimistic numGroupsLimit scan's segment table: no keep bitsets, no first-doc tables (copied after every
   // device pointer above is fixed up: r3 copied it before, so FK_CONJ set leaves scanned with null bitsets)

@@ -272,6 +272,114 @@ void raw_forward_index_decode(const uint8_t* buf, uint64_t size, int32_t data_ty
     if (e) std::rethrow_exception(e);
 }
 
+// VarByteChunkForwardIndexWriter.java (read by VarByteChunkSVForwardIndexReader.java:82-195): the file header of the
+// fixed-byte format above (lengthOfLongestEntry = the longest value), chunk offsets int32 (version 2) or int64
+// (version 3).  A chunk is numDocsPerChunk int32 BE value start offsets from the chunk's start (0 for the missing
+// entries of a partial last chunk), then the values; a value ends where the next one starts, the last one at the
+// chunk's end.  Compressed chunks are compressed whole (header and values).  Version 4 is another format
+// (VarByteChunkForwardIndexWriterV4) and stays PH_ERR_UNSUPPORTED.
+void var_byte_forward_index_read(const uint8_t* buf, uint64_t size, int64_t num_docs,
+                                 const std::function<void(int64_t, const uint8_t*, size_t)>& emit) {
+  if (!buf || size < 28) corrupt("var-byte header too small");
+  const int32_t version = (int32_t)rd_be32(buf);
+  const int64_t nchunks = (int32_t)rd_be32(buf + 4);
+  const int64_t per_chunk = (int32_t)rd_be32(buf + 8);
+  const int64_t entry = (int32_t)rd_be32(buf + 12);
+  const int64_t total = (int32_t)rd_be32(buf + 16);
+  const int32_t comp = (int32_t)rd_be32(buf + 20);
+  const uint64_t data_header = rd_be32(buf + 24);
+  if (version == 4) fail(PH_ERR_UNSUPPORTED, "raw forward index: var-byte writer version 4");
+  if (version != 2 && version != 3) corrupt("unknown var-byte version");
+  if (num_docs < 0 || num_docs > total) corrupt("more docs than the var-byte index holds");
+  if (nchunks < 0 || per_chunk <= 0 || entry < 0 || nchunks * per_chunk < num_docs) corrupt("chunks do not cover the docs");
+  const int off_size = version == 2 ? 4 : 8;
+  if (data_header < 28 || data_header > size || (uint64_t)nchunks * off_size > size - data_header)
+    corrupt("chunk offsets beyond the buffer");
+  if (comp == 2 && !zstd().decompress) fail(PH_ERR_UNSUPPORTED, "raw forward index: ZSTANDARD needs libzstd.so.1");
+  if (comp < 0 || comp > 4) corrupt("unknown compression type");
+  auto chunk_pos = [&](int64_t c) -> uint64_t {
+    const uint8_t* p = buf + data_header + (uint64_t)c * off_size;
+    return off_size == 4 ? rd_be32(p) : rd_be64(p);
+  };
+  const uint64_t hdr = (uint64_t)per_chunk * 4;
+  const uint64_t chunk_bytes = (uint64_t)per_chunk * (4 + (uint64_t)entry);  // the writer's chunk buffer
+  if (comp != 0 && chunk_bytes > (1ull << 28)) corrupt("var-byte chunk size");
+  std::vector<uint8_t> tmp;
+  for (int64_t c = 0; c * per_chunk < num_docs; ++c) {
+    const int64_t d0 = c * per_chunk;
+    const int64_t nd = std::min<int64_t>(per_chunk, num_docs - d0);
+    const uint64_t pos = chunk_pos(c);
+    const uint64_t end = c + 1 < nchunks ? chunk_pos(c + 1) : size;
+    if (pos > end || end > size) corrupt("chunk out of the buffer");
+    const uint8_t* chunk = buf + pos;
+    uint64_t clen = end - pos;
+    if (comp != 0) {
+      tmp.resize((size_t)chunk_bytes);
+      size_t got;
+      if (comp == 1) {
+        got = snappy_decompress(chunk, clen, tmp.data(), tmp.size());
+      } else if (comp == 2) {
+        got = zstd().decompress(tmp.data(), tmp.size(), chunk, clen);
+        if (zstd().is_error(got)) corrupt("bad ZSTANDARD chunk");
+      } else if (comp == 3) {
+        got = lz4_block_decompress(chunk, clen, tmp.data(), tmp.size());
+      } else {  // LZ4_LENGTH_PREFIXED
+        if (clen < 4) corrupt("short LZ4 length prefix");
+        const size_t want = (size_t)chunk[0] | ((size_t)chunk[1] << 8) | ((size_t)chunk[2] << 16) | ((size_t)chunk[3] << 24);
+        got = lz4_block_decompress(chunk + 4, clen - 4, tmp.data(), tmp.size());
+        if (got != want) corrupt("LZ4 chunk length differs from its prefix");
+      }
+      chunk = tmp.data();
+      clen = got;
+    }
+    if (clen < hdr) corrupt("var-byte chunk shorter than its offsets");
+    for (int64_t r = 0; r < nd; ++r) {
+      const uint64_t start = rd_be32(chunk + 4 * r);
+      uint64_t stop = clen;
+      if (r + 1 < per_chunk) {
+        const uint64_t next = rd_be32(chunk + 4 * (r + 1));
+        if (next != 0) stop = next;  // 0: no next entry in this (last, partial) chunk
+      }
+      if (start < hdr || start > stop || stop > clen) corrupt("var-byte value offset out of the chunk");
+      emit(d0 + r, chunk + start, (size_t)(stop - start));
+    }
+  }
+}
+
+// ObjectSerDeUtils' HyperLogLog bytes (HYPER_LOG_LOG_SER_DE: HyperLogLog.getBytes): int32 BE log2m, int32 BE byte size
+// of the register words, then clearspring RegisterSet words (int32 BE, six 5-bit registers each; m / 6 + 1 of them)
+void hll_pair_column_parse(const uint8_t* buf, uint64_t size, int64_t num_docs, const std::string& pair, int32_t* log2m,
+                           std::vector<uint32_t>* words) {
+  auto bad = [&](const std::string& what) { fail(PH_ERR_INVALID_ARGUMENT, "star-tree pair " + pair + ": " + what); };
+  if (num_docs <= 0) bad("no records");
+  int32_t lm = 0;
+  size_t nw = 0;
+  try {
+    var_byte_forward_index_read(buf, size, num_docs, [&](int64_t doc, const uint8_t* p, size_t len) {
+      if (len < 8) bad("HyperLogLog value shorter than its header");
+      const int32_t l = (int32_t)rd_be32(p);
+      if (l < 1 || l > 16) bad("HyperLogLog log2m out of 1..16");
+      if (doc == 0) {
+        lm = l;
+        nw = ((size_t)1 << l) / 6 + 1;
+        if (words) words->assign((size_t)num_docs * nw, 0);
+      } else if (l != lm) {
+        bad("records of different log2m");
+      }
+      if (rd_be32(p + 4) != 4 * nw) bad("HyperLogLog size field differs from its log2m");
+      if (len != 8 + 4 * nw) bad("HyperLogLog value length differs from its log2m");
+      if (words) {
+        uint32_t* o = words->data() + (size_t)doc * nw;
+        for (size_t w = 0; w < nw; ++w) o[w] = rd_be32(p + 8 + 4 * w);
+      }
+    });
+  } catch (const Error& e) {
+    if (e.code != PH_ERR_INVALID_ARGUMENT || e.msg.compare(0, 15, "star-tree pair ") == 0) throw;
+    bad(e.msg);
+  }
+  if (log2m) *log2m = lm;
+}
+
 void raw_dictionary_encode(int32_t data_type, const void* values, int64_t n, Dictionary* dict, std::vector<int32_t>* ids) {
   dict->type = data_type;
   ids->resize((size_t)n);

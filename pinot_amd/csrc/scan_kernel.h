@@ -718,6 +718,16 @@ __device__ __forceinline__ void process_tile(const KParams& p, SegPtr S, uint8_t
 #pragma unroll
       for (int h = 0; h < kMaxHll; ++h) {
         if (!LATE || h >= p.num_hll) continue;
+        if constexpr (LATE == 2) {
+          // a sketch slot (uniform per slot): the record's registers are merged by k_hll_sketch_merge after the scan.
+          // In MODE_AGG / MODE_GROUP_LDS the row of the global table equals the row lds_hll is flushed to.
+          if (p.hll_words[h]) {
+            const uint32_t at = atomicAdd(p.sk_count, 1u);
+            if (at < p.sk_cap)
+              p.sk_list[at] = ((unsigned long long)(S->sk_doc_base + doc) << 32) | (uint32_t)((g * p.num_hll + h) * m);
+            continue;
+          }
+        }
         ColRef col = S->cols[p.hll_slot[h]];
         const uint32_t e = gld(col.hll + unpack_col(col, doc));
         const int64_t ri = (g * p.num_hll + h) * m + (e >> 8);
@@ -828,6 +838,9 @@ __device__ __forceinline__ void process_tile(const KParams& p, SegPtr S, uint8_t
   }
 }
 
+// LATE: 0 = the next tile's loads are issued before this tile's decode, 1 = after it (a decode that gathers), 2 = 1
+// with DISTINCTCOUNTHLL slots that read star-tree sketch columns (scan_hll_sketch.hip; only sketch queries
+// instantiate it, so no other query carries the append).
 // Persistent grid over the chunk list.  A chunk (<= 256 words of one segment) is processed in rounds: in
 // round r wave w takes tile r * kWaves + w.  Rounds are workgroup-uniform (MODE_PARTITION flushes at round
 // boundaries with workgroup barriers); the other modes never synchronise inside the loop.

@@ -4,7 +4,9 @@
 //   load      StarTreeLoaderUtils / StarTreeIndexContainer (pinot-segment-local/.../startree/v2/store/): the STAR_TREE
 //             buffer (OffHeapStarTree.java:45-83, OffHeapStarTreeNode.java:29-158) parsed on the host; the records'
 //             dimension forward indexes (fixed-bit dictIds of the segment's dictionaries) and function-column pair
-//             columns (raw LONG / DOUBLE) pinned as a segment of their own (the "view")
+//             columns (raw LONG / DOUBLE) pinned as a segment of their own (the "view"); a distinctCountHLL__<col>
+//             pair (BYTES: one serialized HyperLogLog per record, BaseSingleTreeBuilder.java:476-479) as a "sketch
+//             column" of the view: the records' RegisterSet words in HBM
 //   choose    GroupByPlanNode.java:77-99 / AggregationPlanNode.java:100-141 with StarTreeUtils.java:56-214: skipStarTree
 //             unset; an aggregation-only query goes to FastFilteredCountOperator / NonScanBasedAggregationOperator
 //             first; every aggregation a function-column pair of the tree; the filter an AND of per-column predicates
@@ -13,7 +15,8 @@
 //             or group-by, aggregated documents once every predicate and group-by column is consumed, leaf ranges and
 //             the remaining predicate columns otherwise
 //   execute   the view with the query rewritten onto its pair columns (COUNT -> SUM(count__*), SUM / MIN / MAX(c)
-//             -> SUM(sum__c) / MIN(min__c) / MAX(max__c)) and its filter = the traversal's documents AND the
+//             -> SUM(sum__c) / MIN(min__c) / MAX(max__c), DISTINCTCOUNTHLL(c) -> the sketch column
+//             distinctCountHLL__c, merged register-wise by k_hll_sketch_merge) and its filter = the traversal's documents AND the
 //             remaining composites (StarTreeFilterOperator.getFilterOperator :157-199): the same kernels as any query;
 //             the segments the star-tree does not serve run as usual and the two results merge by group value
 #include <algorithm>
@@ -253,6 +256,16 @@ StarTree* choose_tree(const ph_query* q, ph_segment* seg, std::vector<ColPreds>*
     if (!fits) continue;
     for (auto& p : pairs)
       if (!t->served.count(p)) fail(PH_ERR_UNSUPPORTED, "star-tree pair " + p + " is not on the GPU path");
+    // a sketch of another log2m cannot be merged (the reference's HyperLogLog.addAll throws on the size mismatch):
+    // the CPU plan decides
+    for (int k = 0; k < q->num_aggregations; ++k) {
+      const ph_aggregation& a = q->aggregations[k];
+      if (a.type != PH_AGG_DISTINCTCOUNTHLL) continue;
+      const Column& c = *t->view->columns.at(pairs[(size_t)k]);
+      if (c.sketch_log2m != (a.log2m > 0 ? a.log2m : 8))
+        fail(PH_ERR_UNSUPPORTED, "star-tree pair " + pairs[(size_t)k] + " holds log2m " + std::to_string(c.sketch_log2m) +
+                                     ", the query asks for " + std::to_string(a.log2m > 0 ? a.log2m : 8));
+    }
     return t.get();
   }
   return nullptr;
@@ -492,7 +505,8 @@ ph_result* star_tree_execute(Context* ctx, const ph_query* q, ph_segment* const*
 }
 
 // ph_segment_add_star_tree: the view holds the dimensions (the segment's dictionaries re-serialised for the pin) and
-// the count / sum / min / max pair columns (raw: dictionary-encoded at pin like any raw column)
+// the count / sum / min / max pair columns (raw: dictionary-encoded at pin like any raw column); a distinctCountHLL
+// pair's serialized HyperLogLogs are validated, byte-swapped and pinned as the view's sketch column
 void star_tree_add_impl(ph_segment* seg, const ph_star_tree_desc* d) {
   if (!seg || !d) fail(PH_ERR_INVALID_ARGUMENT, "null argument");
   if (seg->parent_docs >= 0) fail(PH_ERR_INVALID_ARGUMENT, "a star-tree view has no star-trees");
@@ -513,6 +527,12 @@ void star_tree_add_impl(ph_segment* seg, const ph_star_tree_desc* d) {
       fail(PH_ERR_INVALID_ARGUMENT, "star-tree leaf documents out of range");
   }
   std::vector<ph_column_desc> cols;
+  struct Sketch {
+    std::string name;
+    int32_t log2m = 0;
+    std::vector<uint32_t> words;
+  };
+  std::vector<Sketch> sketches;
   std::vector<std::vector<uint8_t>> dict_bytes;
   dict_bytes.reserve((size_t)d->num_dimensions);
   for (int32_t i = 0; i < d->num_dimensions; ++i) {
@@ -557,6 +577,15 @@ void star_tree_add_impl(ph_segment* seg, const ph_star_tree_desc* d) {
     const size_t sep = name.find("__");
     const std::string fn = sep == std::string::npos ? name : name.substr(0, sep);
     const bool ours = fn == "count" || fn == "sum" || fn == "min" || fn == "max";
+    if (fn == "distinctCountHLL" && d->metric_forward_index && d->metric_forward_index[i]) {
+      Sketch sk;
+      sk.name = name;
+      hll_pair_column_parse(static_cast<const uint8_t*>(d->metric_forward_index[i]),
+                            d->metric_forward_index_size ? d->metric_forward_index_size[i] : 0, d->num_docs, name,
+                            &sk.log2m, &sk.words);
+      sketches.push_back(std::move(sk));
+      continue;
+    }
     if (!ours || !d->metric_forward_index || !d->metric_forward_index[i]) continue;
     ph_column_desc cd{};
     cd.name = d->metrics[i];
@@ -575,9 +604,25 @@ void star_tree_add_impl(ph_segment* seg, const ph_star_tree_desc* d) {
   vd.columns = cols.data();
   ph_segment* v = segment_pin_impl(seg->ctx, &vd);
   v->parent_docs = seg->num_docs;
-  t->view = v;
+  t->view = v;  // (owned from here: a failed sketch pin frees it with the tree)
+  for (auto& sk : sketches) {
+    auto col = std::make_unique<Column>();
+    col->name = sk.name;
+    col->data_type = PH_INT;
+    col->sketch_log2m = sk.log2m;
+    col->sketch_words = (int32_t)(sk.words.size() / (size_t)d->num_docs);
+    col->d_sketch.alloc(sk.words.size() * sizeof(uint32_t), seg->ctx->device);
+    copy_h2d_sync(col->d_sketch.ptr, sk.words.data(), sk.words.size() * sizeof(uint32_t));
+    v->device_bytes += (int64_t)col->d_sketch.bytes;
+    v->columns[sk.name] = std::move(col);
+    t->served.insert(sk.name);
+  }
   seg->device_bytes += v->device_bytes;
   seg->star_trees.push_back(std::move(t));
+}
+
+void star_tree_hll_pair_check_impl(const void* buf, uint64_t size, int32_t num_docs, int32_t* log2m) {
+  hll_pair_column_parse(static_cast<const uint8_t*>(buf), size, num_docs, "distinctCountHLL", log2m, nullptr);
 }
 
 void star_tree_check_impl(const void* tree, uint64_t size, int32_t* num_nodes, int32_t* num_dimensions) {

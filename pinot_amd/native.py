@@ -139,7 +139,7 @@ EXPORTED_SYMBOLS = (
     "ph_query_dense_layout", "ph_query_execute_dense", "ph_dense_finalize", "ph_fixed_bit_pack",
     "ph_raw_forward_index_read", "ph_index_map_lookup", "ph_result_datatable", "ph_selftest_unpack",
     "ph_selftest_unpack_staged", "ph_last_error", "ph_version", "ph_segment_add_star_tree", "ph_segment_num_star_trees",
-    "ph_star_tree_check",
+    "ph_star_tree_check", "ph_star_tree_hll_pair_check",
 )
 
 _lib = None
@@ -219,6 +219,7 @@ def lib():
         "ph_segment_add_star_tree": ([vp, vp], ctypes.c_int),
         "ph_segment_num_star_trees": ([vp], i32),
         "ph_star_tree_check": ([vp, ctypes.c_uint64, ctypes.POINTER(i32), ctypes.POINTER(i32)], ctypes.c_int),
+        "ph_star_tree_hll_pair_check": ([vp, ctypes.c_uint64, i32, ctypes.POINTER(i32)], ctypes.c_int),
         "ph_last_error": ([], ctypes.c_char_p),
         "ph_version": ([], ctypes.c_char_p),
     }

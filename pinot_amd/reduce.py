@@ -58,9 +58,9 @@ def hll_serialize(registers: np.ndarray, log2m: int) -> bytes:
     (ObjectSerDeUtils.java:535-560, HyperLogLogUtils.java:28-43)."""
     m = 1 << log2m
     nwords = m // 6 + 1
-    words = np.zeros(nwords, dtype=np.uint32)
-    for i in range(m):
-        words[i // 6] |= np.uint32(int(registers[i]) & 0x1F) << np.uint32(5 * (i % 6))
+    regs = np.zeros(nwords * 6, dtype=np.uint32)
+    regs[:m] = np.asarray(registers[:m], dtype=np.uint32) & 0x1F
+    words = (regs.reshape(nwords, 6) << (5 * np.arange(6, dtype=np.uint32))).sum(axis=1, dtype=np.uint32)
     return (np.array([log2m, 4 * nwords], dtype=">i4").tobytes() + words.astype(">u4").tobytes())
 
 

@@ -419,6 +419,32 @@ def write_raw_forward_index(values, data_type: str, compression: str = "PASS_THR
     return np.frombuffer(head + b"".join(chunks), dtype=np.uint8)
 
 
+def write_var_byte_raw_forward_index(values, docs_per_chunk: int = 1000) -> np.ndarray:
+    """VarByteChunkForwardIndexWriter as SingleValueVarByteRawIndexCreator uses it for a BYTES column (PASS_THROUGH,
+    writer version 2, 1000 docs per chunk): the chunk forward index header, int32 chunk offsets, then per chunk
+    docs_per_chunk int32 BE value start offsets (0 for the missing entries of a partial last chunk) and the values."""
+    vals = [bytes(v) for v in values]
+    n = len(vals)
+    nchunks = (n + docs_per_chunk - 1) // docs_per_chunk
+    header = 7 * 4 + nchunks * 4
+    chunks, offsets, pos = [], [], header
+    for c in range(nchunks):
+        part = vals[c * docs_per_chunk:(c + 1) * docs_per_chunk]
+        starts = np.zeros(docs_per_chunk, ">i4")
+        at = 4 * docs_per_chunk
+        for i, v in enumerate(part):
+            starts[i] = at
+            at += len(v)
+        body = starts.tobytes() + b"".join(part)
+        offsets.append(pos)
+        chunks.append(body)
+        pos += len(body)
+    longest = max((len(v) for v in vals), default=0)
+    head = np.array([2, nchunks, docs_per_chunk, longest, n, COMPRESSION["PASS_THROUGH"], 28], ">i4").tobytes()
+    head += np.array(offsets, ">i4").tobytes()
+    return np.frombuffer(head + b"".join(chunks), dtype=np.uint8)
+
+
 def read_raw_forward_index(buf: np.ndarray, data_type: str, num_docs: int) -> np.ndarray:
     """ph_raw_forward_index_read: the library's host decoder of a raw forward index (native-endian values)."""
     out = np.empty(num_docs, dtype=_NATIVE[data_type])

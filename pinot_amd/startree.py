@@ -29,12 +29,14 @@ from typing import Dict, List, Sequence
 import numpy as np
 
 from . import native as N
-from .segment import fixed_bit_pack, num_bits_per_value, write_raw_forward_index
+from .reduce import hll_serialize
+from .segment import fixed_bit_pack, num_bits_per_value, write_raw_forward_index, write_var_byte_raw_forward_index
 
 MAGIC = 0xBADDA55B00DAD00D
 ALL = -1                   # StarTreeNode.ALL
 STAR_IN_FORWARD_INDEX = 0  # StarTreeV2Constants.STAR_IN_FORWARD_INDEX
-FUNCTIONS = ("count", "sum", "min", "max")  # AggregationFunctionType.getName() of the supported pairs
+HLL = "distinctCountHLL"
+FUNCTIONS = ("count", "sum", "min", "max", HLL)  # AggregationFunctionType.getName() of the supported pairs
 
 
 @dataclass
@@ -45,7 +47,8 @@ class StarTreeBuffers:
     pairs: List[str]                      # function-column pair column names, e.g. "count__*", "sum__m"
     tree: np.ndarray                      # the STAR_TREE buffer (OffHeapStarTree format)
     dim_fwd: Dict[str, np.ndarray]        # fixed-bit packed dictIds (parent column's bit width)
-    metric_fwd: Dict[str, np.ndarray]     # raw forward indexes (LONG for count__*, DOUBLE otherwise)
+    metric_fwd: Dict[str, np.ndarray]     # raw forward indexes (LONG count__*, var-byte BYTES distinctCountHLL__*,
+                                          # DOUBLE otherwise)
     max_leaf_records: int = 10
     skip_star: List[str] = field(default_factory=list)
     # writer-side copies (tests): the star-tree records
@@ -93,12 +96,12 @@ class _Builder:
         prev = None
         for i in order:
             row = dims[i]
-            raw = [None if k == "count" else float(m[i]) for k, m in zip(kinds, metrics)]
+            raw = [None if k == "count" else (m[i] if k == HLL else float(m[i])) for k, m in zip(kinds, metrics)]
             if prev is not None and np.array_equal(row, prev):
                 self._apply_raw(self.M[-1], raw)
             else:
                 self.D.append(row.copy())
-                self.M.append([1 if k == "count" else v for k, v in zip(kinds, raw)])
+                self.M.append([1 if k == "count" else (v.copy() if k == HLL else v) for k, v in zip(kinds, raw)])
                 prev = row
 
     def _apply_raw(self, agg, raw):
@@ -109,6 +112,8 @@ class _Builder:
                 agg[j] = agg[j] + raw[j]
             elif k == "min":
                 agg[j] = min(agg[j], raw[j])
+            elif k == HLL:  # HyperLogLog.addAll: register-wise max (DistinctCountHLLValueAggregator.java:89-97)
+                agg[j] = np.maximum(agg[j], raw[j])
             else:
                 agg[j] = max(agg[j], raw[j])
 
@@ -120,6 +125,8 @@ class _Builder:
                 agg[j] = agg[j] + other[j]
             elif k == "min":
                 agg[j] = min(agg[j], other[j])
+            elif k == HLL:
+                agg[j] = np.maximum(agg[j], other[j])
             else:
                 agg[j] = max(agg[j], other[j])
         return agg
@@ -232,8 +239,10 @@ class _Builder:
 def build_star_tree(seg, dimensions: Sequence[str], pairs: Sequence[tuple], max_leaf_records: int = 10,
                     skip_star: Sequence[str] = (), values: Dict[str, np.ndarray] = None) -> StarTreeBuffers:
     """A star-tree over `seg` (SegmentBuffers): split order `dimensions` (dictionary columns), function-column
-    `pairs` [(function, column)] with function in count / sum / min / max (column "*" for count); `values` holds the
-    metric columns' raw values (the writer reads them as PinotSegmentColumnReader.getValue would)."""
+    `pairs` [(function, column)] with function in count / sum / min / max / distinctCountHLL (column "*" for count);
+    `values` holds the metric columns' raw values (the writer reads them as PinotSegmentColumnReader.getValue would).
+    For distinctCountHLL, values[col] is a uint8 [num_docs, 2^log2m] array: the registers of each raw document's
+    single-value HyperLogLog; records merge by elementwise max and the pair column holds their serialized bytes."""
     n = seg.num_docs
     dims = np.zeros((n, len(dimensions)), np.int32)
     for j, d in enumerate(dimensions):
@@ -247,7 +256,14 @@ def build_star_tree(seg, dimensions: Sequence[str], pairs: Sequence[tuple], max_
             raise ValueError(f"unsupported star-tree function {fn}")
         kinds.append(fn)
         names.append(pair_name(fn, col))
-        mets.append(None if fn == "count" else np.asarray(values[col], np.float64))
+        if fn == HLL:
+            regs = np.asarray(values[col], np.uint8)
+            m = regs.shape[1] if regs.ndim == 2 else 0
+            if regs.ndim != 2 or len(regs) != n or m < 2 or m & (m - 1):
+                raise ValueError(f"distinctCountHLL values of {col}: uint8 [num_docs, 2^log2m] registers")
+            mets.append(regs)
+        else:
+            mets.append(None if fn == "count" else np.asarray(values[col], np.float64))
     b = _Builder(dims, mets, kinds, max_leaf_records, {dimensions.index(s) for s in skip_star})
     root = _Node(-1, ALL, 0, len(b.D))
     b.construct(root, 0, len(b.D))
@@ -258,6 +274,12 @@ def build_star_tree(seg, dimensions: Sequence[str], pairs: Sequence[tuple], max_
     dim_fwd = {d: fixed_bit_pack(D[:, j], seg.columns[d].bits) for j, d in enumerate(dimensions)}
     metrics, metric_fwd = {}, {}
     for j, (nm, k) in enumerate(zip(names, kinds)):
+        if k == HLL:
+            col = np.array([m[j] for m in b.M], np.uint8).reshape(nd, -1)
+            log2m = col.shape[1].bit_length() - 1
+            metrics[nm] = col
+            metric_fwd[nm] = write_var_byte_raw_forward_index([hll_serialize(r, log2m) for r in col])
+            continue
         col = np.array([m[j] for m in b.M], np.int64 if k == "count" else np.float64)
         metrics[nm] = col
         metric_fwd[nm] = write_raw_forward_index(col, "LONG" if k == "count" else "DOUBLE")
