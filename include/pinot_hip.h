@@ -145,8 +145,22 @@ typedef struct {
   int32_t predicate;            /* PREDICATE: index into ph_query.predicates */
 } ph_filter_node;
 
-typedef enum { PH_AGG_COUNT = 0, PH_AGG_SUM = 1, PH_AGG_MIN = 2, PH_AGG_MAX = 3, PH_AGG_DISTINCTCOUNTHLL = 4 }
-    ph_aggregation_type;
+/* PH_AGG_DISTINCTCOUNT: the exact distinct count of any pinned single-value column (INT, LONG, FLOAT, DOUBLE or STRING;
+ * a raw column too: the pin dictionary-encodes it), evaluated in dictId space like the reference
+ * (BaseDistinctAggregateAggregationFunction.java:133-168: a RoaringBitmap of dictIds per result holder).  log2m and
+ * column2 are ignored; a non-NONE expr_op is PH_ERR_UNSUPPORTED.  Shapes that return PH_ERR_UNSUPPORTED (the caller's
+ * CPU plan serves them): multi-device contexts, the dense-partial entry points, segment group trim
+ * (min_segment_group_trim_size > 0 with ORDER BY), bitset tables beyond the dense table budget (32 GB, the device table
+ * plus the host copy of the rows that can be non-empty) and group key spaces beyond the dense group tables.  A query
+ * holding a DISTINCTCOUNT is never answered from a star-tree: it scans the segment's own docs. */
+typedef enum {
+  PH_AGG_COUNT = 0,
+  PH_AGG_SUM = 1,
+  PH_AGG_MIN = 2,
+  PH_AGG_MAX = 3,
+  PH_AGG_DISTINCTCOUNTHLL = 4,
+  PH_AGG_DISTINCTCOUNT = 5
+} ph_aggregation_type;
 
 /* 2-operand expression argument of SUM / MIN / MAX: `column <op> column2`, evaluated per row like the reference's
  * TransformOperator (ProjectPlanNode.java:82, AggregationFunctionUtils.java:86): MultiplicationTransformFunction
@@ -245,8 +259,12 @@ enum {
   /* 13: retired (round 4's wave-private-ring kernel A, removed in round 5) */
   PH_KERNEL_AGG_CONTAINERS = 14, /* k_agg_sparse straight from the roaring containers of an EQ / IN inverted leaf
                                     (no doc bitmaps; BitmapInvertedIndexReader.java:45-62) */
-  PH_KERNEL_GROUP_CONTAINERS = 15 /* k_group_sparse with each chunk's leaf bitmaps built in LDS from the roaring
+  PH_KERNEL_GROUP_CONTAINERS = 15,/* k_group_sparse with each chunk's leaf bitmaps built in LDS from the roaring
                                      containers (no doc bitmaps in HBM) */
+  PH_KERNEL_SCAN_DISTINCT_LDS = 16, /* k_scan<MODE, ..., LATE = 3>: DISTINCTCOUNT bitsets in the workgroup's LDS, flushed
+                                       to the HBM table at the end (plan_mode 1 when they fit, plan_mode 2) */
+  PH_KERNEL_SCAN_DISTINCT_HBM = 17  /* k_scan<MODE, ..., LATE = 3>: DISTINCTCOUNT bits ORed straight into the HBM table
+                                       (plan_mode 1 otherwise, plan_mode 3) */
 };
 
 /* ------------------------------------------------------------------ context */
@@ -395,9 +413,28 @@ int ph_result_group_keys(const ph_result* r, int32_t group_by_index, void* out);
  * their context) */
 const void* ph_result_key_data(const ph_result* r, int32_t group_by_index);
 /* intermediate result of aggregation i for every row: COUNT int64, SUM/MIN/MAX double,
- * DISTINCTCOUNTHLL uint8[2^log2m] raw registers (HyperLogLog.addAll = register-wise max) */
+ * DISTINCTCOUNTHLL uint8[2^log2m] raw registers (HyperLogLog.addAll = register-wise max),
+ * DISTINCTCOUNT uint32[W] bitset over the aggregation's result dictionary, W = ceil(D / 32): bit i & 31 of word
+ * i >> 5 set means value i of the dictionary is present; bits past D are zero */
 int ph_result_aggregation(const ph_result* r, int32_t aggregation_index, void* out);
 const void* ph_result_aggregation_data(const ph_result* r, int32_t aggregation_index);
+/* DISTINCTCOUNT aggregation k.  Its result dictionary is the table dictionary of the column (ph_table_set_dictionary)
+ * or, without one, the sorted value union of the column over the queried segments; the reference converts its dictId
+ * bitmap to a value set only when the result is extracted (BaseDistinctAggregateAggregationFunction.java:77-108) and
+ * the final result is that set's size as INT (DistinctCountAggregationFunction.java:61-68).  Results of different
+ * calls may have different dictionaries: merge them by value.
+ *   ph_result_distinct_dictionary  stored ph_data_type, bytes per value and the number of values D
+ *   ph_result_distinct_values      the D values ascending, laid out as ph_result_key_data lays out group keys
+ *                                  (valid until ph_result_destroy)
+ *   ph_result_distinct_words       W, the uint32 words of a row's bitset (-1: not a DISTINCTCOUNT aggregation)
+ *   ph_result_distinct_counts      int32 per result row: the bitset's popcount, computed on the device
+ * With no filter and no group-by the aggregation is answered from metadata like the reference's dictionary-based
+ * operator (AggregationPlanNode.java:108-119): every value of every segment's dictionary, plan_mode -1. */
+int ph_result_distinct_dictionary(const ph_result* r, int32_t aggregation_index, int32_t* data_type, int32_t* entry_size,
+                                  int64_t* count);
+const void* ph_result_distinct_values(const ph_result* r, int32_t aggregation_index);
+int32_t ph_result_distinct_words(const ph_result* r, int32_t aggregation_index);
+int ph_result_distinct_counts(const ph_result* r, int32_t aggregation_index, int32_t* out);
 
 /* ------------------------------------------------------------------ server -> broker DataTable */
 /* The result as the DataTable V4 bytes the reference's server returns for it (InstanceResponseBlock.toDataTable:
@@ -405,7 +442,12 @@ const void* ph_result_aggregation_data(const ph_result* r, int32_t aggregation_i
  * DataTableImplV4.toBytes): group-by identifiers + one intermediate-result column per aggregation, results metadata
  * (BaseResultsBlock.getResultsMetadata) followed by the caller's `extra` entries (e.g. numSegmentsQueried,
  * timeUsedMs, requestId; MetadataKey names, DataTable.java:103-137), in java.util.HashMap order.  `q` is the query
- * the result came from (column names).  out == NULL: only *size is set; otherwise capacity must be >= *size. */
+ * the result came from (column names).  out == NULL: only *size is set; otherwise capacity must be >= *size.
+ * A DISTINCTCOUNT column is OBJECT: the reference's value-set serialisation chosen by stored type as convertToValueSet
+ * does -- IntSet(9), LongSet(15), FloatSet(16), DoubleSet(17), StringSet(18) (ObjectSerDeUtils.java:113-123, serialisers
+ * :725-891): int32 BE size, then the values (strings: int32 BE length + UTF-8).  Values are written ascending; the
+ * reference writes its fastutil set's iteration order and its deserialisers do not depend on the order, so the bytes
+ * are an equal set, not byte-identical (parity unpinned). */
 typedef struct {
   const char* key;
   const char* value;

@@ -25,7 +25,8 @@ import org.apache.pinot.segment.spi.AggregationFunctionType;
  * QueryContext -> the ph_query descriptor of PinotHipJni.queryExecute (the Java twin of pinot_amd/query.py +
  * engine._QueryStruct).  Returns null for shapes outside the GPU path, so the plan maker keeps the CPU plan:
  * filtered aggregations, star-tree, null handling, non-identifier group-by expressions, aggregations other than
- * COUNT / SUM / MIN / MAX / DISTINCTCOUNTHLL (over a column or a 2-operand mult/sub/add), predicates other than
+ * COUNT / SUM / MIN / MAX / DISTINCTCOUNTHLL / DISTINCTCOUNT (over a column; SUM / MIN / MAX also over a 2-operand
+ * mult/sub/add), predicates other than
  * EQ / NOT_EQ / IN / NOT_IN / RANGE on identifiers, and a segment group trim (GroupByOperator.java:114-130) ordered
  * by anything but group-by columns and aggregations.
  */
@@ -281,6 +282,9 @@ public final class GpuQuery {
         case DISTINCTCOUNTHLL:
           type = PinotHipJni.AGG_DISTINCTCOUNTHLL;
           break;
+        case DISTINCTCOUNT:  // exact: a bitset over the column's result dictionary (ph_result_distinct_*)
+          type = PinotHipJni.AGG_DISTINCTCOUNT;
+          break;
         default:
           return null;
       }
@@ -290,7 +294,8 @@ public final class GpuQuery {
         return new int[]{type, str(e.getIdentifier()), log2m, -1, PinotHipJni.EXPR_NONE};
       }
       // SUM(a*b) / SUM(a-b) / SUM(a+b): one 2-operand transform over identifiers (ProjectPlanNode.java:82)
-      if (e.getType() == ExpressionContext.Type.FUNCTION && type != PinotHipJni.AGG_DISTINCTCOUNTHLL) {
+      if (e.getType() == ExpressionContext.Type.FUNCTION && type != PinotHipJni.AGG_DISTINCTCOUNTHLL
+          && type != PinotHipJni.AGG_DISTINCTCOUNT) {
         FunctionContext fn = e.getFunction();
         int op = "times".equals(fn.getFunctionName()) || "mult".equals(fn.getFunctionName()) ? PinotHipJni.EXPR_MULT
             : "minus".equals(fn.getFunctionName()) || "sub".equals(fn.getFunctionName()) ? PinotHipJni.EXPR_SUB

@@ -1,5 +1,13 @@
 package org.apache.pinot.core.gpu;
 
+import it.unimi.dsi.fastutil.doubles.DoubleOpenHashSet;
+import it.unimi.dsi.fastutil.floats.FloatOpenHashSet;
+import it.unimi.dsi.fastutil.ints.IntOpenHashSet;
+import it.unimi.dsi.fastutil.longs.LongOpenHashSet;
+import it.unimi.dsi.fastutil.objects.ObjectOpenHashSet;
+import java.nio.ByteBuffer;
+import java.nio.ByteOrder;
+import java.nio.charset.StandardCharsets;
 import java.util.List;
 import org.apache.pinot.common.request.context.ExpressionContext;
 import org.apache.pinot.common.utils.DataSchema;
@@ -11,7 +19,9 @@ import org.apache.pinot.core.query.request.context.QueryContext;
 /**
  * The DataSchema of a GPU group-by result, as GroupByOperator builds it (GroupByOperator.java:66-86): the group-by
  * expressions with the stored types of their key columns, then each function's result column name and intermediate
- * type.
+ * type.  Also the intermediate result of DISTINCTCOUNT: the value set the reference's convertToValueSet builds from its
+ * dictId bitmap (BaseDistinctAggregateAggregationFunction.java:77-108), here from the result dictionary's values x the
+ * row's bitset.  (Written against the reference API; not compiled in this repository's build.)
  */
 final class GpuResultSchema {
   private GpuResultSchema() {
@@ -24,6 +34,66 @@ final class GpuResultSchema {
       case PinotHipJni.FLOAT: return ColumnDataType.FLOAT;
       case PinotHipJni.DOUBLE: return ColumnDataType.DOUBLE;
       default: return ColumnDataType.STRING;
+    }
+  }
+
+  /** DISTINCTCOUNT aggregation {@code k} of a result: its dictionary and buffers are fetched once (three JNI calls, two
+   *  direct buffers over the whole column), then {@link #set} builds any row's value set from them. */
+  static final class DistinctColumn {
+    private final int _type;
+    private final int _entrySize;
+    private final int _words;
+    private final long _count;
+    private final ByteBuffer _bits;
+    private final ByteBuffer _values;
+
+    DistinctColumn(long res, int k) {
+      int[] tew = new int[3];
+      _count = PinotHipJni.resultDistinctDictionary(res, k, tew);
+      _type = tew[0];
+      _entrySize = tew[1];
+      _words = tew[2];
+      _bits = PinotHipJni.resultAggregationBuffer(res, k, 4 * _words).order(ByteOrder.nativeOrder());
+      _values = PinotHipJni.resultDistinctValues(res, k).order(ByteOrder.nativeOrder());
+    }
+
+    /** Row {@code row}: IntOpenHashSet / LongOpenHashSet / FloatOpenHashSet / DoubleOpenHashSet /
+     *  ObjectOpenHashSet<String> by the column's stored type. */
+    Object set(int row) {
+      IntOpenHashSet ints = _type == PinotHipJni.INT ? new IntOpenHashSet() : null;
+      LongOpenHashSet longs = _type == PinotHipJni.LONG ? new LongOpenHashSet() : null;
+      FloatOpenHashSet floats = _type == PinotHipJni.FLOAT ? new FloatOpenHashSet() : null;
+      DoubleOpenHashSet doubles = _type == PinotHipJni.DOUBLE ? new DoubleOpenHashSet() : null;
+      ObjectOpenHashSet<String> strings = _type == PinotHipJni.STRING ? new ObjectOpenHashSet<>() : null;
+      int es = _entrySize;
+      for (int word = 0; word < _words; word++) {
+        int x = _bits.getInt(4 * (row * _words + word));
+        while (x != 0) {
+          int i = 32 * word + Integer.numberOfTrailingZeros(x);
+          x &= x - 1;
+          if (i >= _count) {
+            break;
+          }
+          switch (_type) {
+            case PinotHipJni.INT: ints.add(_values.getInt(es * i)); break;
+            case PinotHipJni.LONG: longs.add(_values.getLong(es * i)); break;
+            case PinotHipJni.FLOAT: floats.add(_values.getFloat(es * i)); break;
+            case PinotHipJni.DOUBLE: doubles.add(_values.getDouble(es * i)); break;
+            default: {
+              byte[] b = new byte[es];
+              for (int j = 0; j < es; j++) {
+                b[j] = _values.get(es * i + j);
+              }
+              int len = 0;
+              while (len < es && b[len] != 0) {
+                len++;
+              }
+              strings.add(new String(b, 0, len, StandardCharsets.UTF_8));
+            }
+          }
+        }
+      }
+      return ints != null ? ints : longs != null ? longs : floats != null ? floats : doubles != null ? doubles : strings;
     }
   }
 

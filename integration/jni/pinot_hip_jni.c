@@ -351,6 +351,24 @@ JNIEXPORT jobject JNICALL FN(resultAggregationBuffer)(JNIEnv* env, jclass c, jlo
   return (*env)->NewDirectByteBuffer(env, (void*)ph_result_aggregation_data(PTR(res), a), (jlong)n * entryBytes);
 }
 
+/* ph_result_distinct_dictionary + ph_result_distinct_words: out = {data type, entry size, W}; returns the value
+ * count D.  (Uncompiled here: no JDK in this repository's build.) */
+JNIEXPORT jlong JNICALL FN(resultDistinctDictionary)(JNIEnv* env, jclass c, jlong res, jint a, jintArray out) {
+  int32_t type = 0, es = 0;
+  int64_t count = 0;
+  if (throw_ph(env, ph_result_distinct_dictionary(PTR(res), a, &type, &es, &count))) return 0;
+  const jint v[3] = {type, es, ph_result_distinct_words(PTR(res), a)};
+  (*env)->SetIntArrayRegion(env, out, 0, 3, v);
+  return (jlong)count;
+}
+
+JNIEXPORT jobject JNICALL FN(resultDistinctValues)(JNIEnv* env, jclass c, jlong res, jint a) {
+  int32_t type = 0, es = 0;
+  int64_t count = 0;
+  if (throw_ph(env, ph_result_distinct_dictionary(PTR(res), a, &type, &es, &count))) return NULL;
+  return (*env)->NewDirectByteBuffer(env, (void*)ph_result_distinct_values(PTR(res), a), (jlong)count * es);
+}
+
 /* ph_exec_stats: numDocsScanned, numEntriesScannedInFilter, numEntriesScannedPostFilter, numTotalDocs,
  * numSegmentsProcessed, numSegmentsMatched, numGroupsLimitReached */
 JNIEXPORT void JNICALL FN(resultStats)(JNIEnv* env, jclass c, jlong res, jlongArray out) {

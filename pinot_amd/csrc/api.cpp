@@ -321,11 +321,22 @@ int ph_table_set_column_type(ph_ctx* ctx, const char* column, int32_t data_type)
   });
 }
 
+static bool has_distinct_count(const ph_query* q) {
+  for (int32_t k = 0; q && q->aggregations && k < q->num_aggregations; ++k)
+    if (q->aggregations[k].type == PH_AGG_DISTINCTCOUNT) return true;
+  return false;
+}
+
 int ph_query_execute(ph_ctx* ctx, const ph_query* query, ph_segment* const* segments, int32_t num_segments,
                      ph_result** out) {
   return guarded([&] {
     if (!ctx || !out) fail(PH_ERR_INVALID_ARGUMENT, "null argument");
     *out = nullptr;
+    // DISTINCTCOUNT bitsets are neither merged across devices nor trimmed per segment: the CPU plan serves those
+    if (has_distinct_count(query) && ctx->devs.size() > 1)
+      fail(PH_ERR_UNSUPPORTED, "DISTINCTCOUNT on a multi-device context");
+    if (has_distinct_count(query) && query->min_segment_group_trim_size > 0 && query->num_group_by > 0 && query->num_order_by > 0)
+      fail(PH_ERR_UNSUPPORTED, "DISTINCTCOUNT with segment group trim (minSegmentGroupTrimSize)");
     if (ctx->devs.size() > 1)
       *out = multi_execute(ctx, query, segments, num_segments);  // per device, merged in the library
     else if (query && query->min_segment_group_trim_size > 0 && query->num_group_by > 0 && query->num_order_by > 0)
@@ -409,7 +420,8 @@ static Context* dense_device(ph_ctx* ctx, ph_segment* const* segs, int32_t n) {
   return c;
 }
 
-static void reject_segment_trim(const ph_query* q) {
+static void reject_dense_shapes(const ph_query* q) {
+  if (has_distinct_count(q)) fail(PH_ERR_UNSUPPORTED, "DISTINCTCOUNT on dense partials");
   if (q && q->min_segment_group_trim_size > 0 && q->num_group_by > 0 && q->num_order_by > 0)
     fail(PH_ERR_UNSUPPORTED, "segment group trim (minSegmentGroupTrimSize) on dense partials");
 }
@@ -418,7 +430,7 @@ int ph_query_dense_layout(ph_ctx* ctx, const ph_query* query, ph_segment* const*
                           ph_dense_layout* out) {
   return guarded([&] {
     if (!ctx || !out) fail(PH_ERR_INVALID_ARGUMENT, "null argument");
-    reject_segment_trim(query);
+    reject_dense_shapes(query);
     DenseArgs d{DENSE_LAYOUT, nullptr, 0, 0, out};
     query_execute_impl(dense_device(ctx, segments, num_segments), query, segments, num_segments, &d);
   });
@@ -428,7 +440,7 @@ int ph_query_execute_dense(ph_ctx* ctx, const ph_query* query, ph_segment* const
                            void* const* device_tables, ph_exec_stats* stats) {
   return guarded([&] {
     if (!ctx || !device_tables) fail(PH_ERR_INVALID_ARGUMENT, "null argument");
-    reject_segment_trim(query);
+    reject_dense_shapes(query);
     DenseArgs d{DENSE_EXECUTE, device_tables, 0, 0, nullptr};
     std::unique_ptr<ph_result> r(query_execute_impl(dense_device(ctx, segments, num_segments), query, segments,
                                                     num_segments, &d));
@@ -441,7 +453,7 @@ int ph_dense_finalize(ph_ctx* ctx, const ph_query* query, ph_segment* const* seg
   return guarded([&] {
     if (!ctx || !device_tables || !out) fail(PH_ERR_INVALID_ARGUMENT, "null argument");
     *out = nullptr;
-    reject_segment_trim(query);
+    reject_dense_shapes(query);
     DenseArgs d{DENSE_FINALIZE, const_cast<void* const*>(device_tables), group_begin, group_end, nullptr};
     *out = query_execute_impl(dense_device(ctx, segments, num_segments), query, segments, num_segments, &d);
   });
@@ -492,6 +504,40 @@ int ph_result_aggregation(const ph_result* r, int32_t k, void* out) {
   return guarded([&] {
     if (!r || !out || k < 0 || k >= (int32_t)r->aggs.size()) fail(PH_ERR_INVALID_ARGUMENT, "bad aggregation index");
     memcpy(out, r->aggs[k].data(), r->aggs[k].size());
+  });
+}
+
+// ---- DISTINCTCOUNT result columns
+static const ph_result::Distinct& distinct_of(const ph_result* r, int32_t k) {
+  if (!r || k < 0 || k >= (int32_t)r->distinct.size() || !r->distinct[k].set)
+    fail(PH_ERR_INVALID_ARGUMENT, "not a DISTINCTCOUNT aggregation");
+  return r->distinct[k];
+}
+
+int ph_result_distinct_dictionary(const ph_result* r, int32_t k, int32_t* data_type, int32_t* entry_size, int64_t* count) {
+  return guarded([&] {
+    const ph_result::Distinct& d = distinct_of(r, k);
+    if (data_type) *data_type = d.data_type;
+    if (entry_size) *entry_size = d.entry_size;
+    if (count) *count = d.count;
+  });
+}
+
+const void* ph_result_distinct_values(const ph_result* r, int32_t k) {
+  if (!r || k < 0 || k >= (int32_t)r->distinct.size() || !r->distinct[k].set) return nullptr;
+  return r->distinct[k].values.data();
+}
+
+int32_t ph_result_distinct_words(const ph_result* r, int32_t k) {
+  if (!r || k < 0 || k >= (int32_t)r->distinct.size() || !r->distinct[k].set) return -1;
+  return r->distinct[k].words;
+}
+
+int ph_result_distinct_counts(const ph_result* r, int32_t k, int32_t* out) {
+  return guarded([&] {
+    const ph_result::Distinct& d = distinct_of(r, k);
+    if (!out) fail(PH_ERR_INVALID_ARGUMENT, "null output");
+    memcpy(out, d.counts.data(), sizeof(int32_t) * d.counts.size());
   });
 }
 

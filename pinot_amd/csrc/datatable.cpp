@@ -10,7 +10,7 @@
 //   Data schema (DataSchema.toBytes): numColumns, UTF-8 names, UTF-8 ColumnDataType names.  Columns: the group-by
 //   identifiers (GroupByOperator.java:76-81; stored types INT / LONG / FLOAT / DOUBLE / STRING) then one column per
 //   aggregation named AggregationFunction.getResultColumnName() (`count(*)`, `sum(m)`, `sum(times(a,b))`) with its
-//   intermediate type (COUNT LONG, SUM / MIN / MAX DOUBLE, DISTINCTCOUNTHLL OBJECT).
+//   intermediate type (COUNT LONG, SUM / MIN / MAX DOUBLE, DISTINCTCOUNTHLL / DISTINCTCOUNT OBJECT).
 //   Fixed-size rows (DataTableUtils.computeColumnOffsets): INT / FLOAT / STRING (a string-dictionary id, assigned in
 //   first-seen order, DataTableBuilderV4.setColumn(String)) 4 bytes, LONG / DOUBLE 8, OBJECT 8 = (offset into the
 //   variable section, byte length); the variable section holds int objectType (ObjectSerDeUtils.ObjectType
@@ -102,9 +102,9 @@ std::vector<std::pair<std::string, std::string>> hashmap_order(const std::vector
 }
 
 std::string agg_column_name(const ph_aggregation& a) {
-  static const char* fn[] = {"count", "sum", "min", "max", "distinctcounthll"};
+  static const char* fn[] = {"count", "sum", "min", "max", "distinctcounthll", "distinctcount"};
   if (a.type == PH_AGG_COUNT) return "count(*)";
-  if (a.type < 0 || a.type > PH_AGG_DISTINCTCOUNTHLL) fail(PH_ERR_INVALID_ARGUMENT, "unknown aggregation");
+  if (a.type < 0 || a.type > PH_AGG_DISTINCTCOUNT) fail(PH_ERR_INVALID_ARGUMENT, "unknown aggregation");
   std::string arg = a.column ? a.column : "";
   if (a.expr_op != PH_EXPR_NONE) {  // FunctionContext.toString of the compiled arithmetic (TransformFunctionType)
     static const char* op[] = {"", "times", "minus", "plus"};
@@ -146,7 +146,7 @@ std::vector<uint8_t> result_to_datatable(const ph_result* r, const ph_query* q, 
   for (int k = 0; k < na; ++k) {
     names.push_back(agg_column_name(q->aggregations[k]));
     const int t = r->agg_types[k];
-    types.push_back(t == PH_AGG_COUNT ? "LONG" : (t == PH_AGG_DISTINCTCOUNTHLL ? "OBJECT" : "DOUBLE"));
+    types.push_back(t == PH_AGG_COUNT ? "LONG" : ((t == PH_AGG_DISTINCTCOUNTHLL || t == PH_AGG_DISTINCTCOUNT) ? "OBJECT" : "DOUBLE"));
     width[nk + k] = 8;
   }
   for (int c = 0; c < ncol; ++c) {
@@ -201,6 +201,36 @@ std::vector<uint8_t> result_to_datatable(const ph_result* r, const ph_query* q, 
         std::vector<uint32_t> w(words, 0);
         for (int j = 0; j < m; ++j) w[j / 6] |= (uint32_t)(reg[j] & 0x1f) << (5 * (j % 6));
         for (uint32_t x : w) var.i32((int32_t)x);
+      } else if (t == PH_AGG_DISTINCTCOUNT) {
+        // the value set convertToValueSet builds from the dictId bitmap (BaseDistinctAggregateAggregationFunction.java:
+        // 77-108), serialised as ObjectSerDeUtils does (:725-891): int objectType, int size, the values (strings: int
+        // length + UTF-8).  Values ascending; the reference writes its fastutil set's iteration order and reads any
+        // order back, so this is the same set but not the same bytes (parity unpinned)
+        if (k >= (int)r->distinct.size() || !r->distinct[k].set) fail(PH_ERR_INVALID_ARGUMENT, "DISTINCTCOUNT result without a dictionary");
+        const ph_result::Distinct& d = r->distinct[k];
+        static const int32_t object_type[] = {9, 15, 16, 17, 18};  // IntSet, LongSet, FloatSet, DoubleSet, StringSet
+        const uint32_t* bits = reinterpret_cast<const uint32_t*>(base) + (size_t)g * d.words;
+        const size_t start = var.b.size();
+        var.i32(object_type[d.data_type]);
+        var.i32(d.counts[(size_t)g]);
+        for (int64_t i = 0; i < d.count; ++i) {
+          if (!((bits[i >> 5] >> (i & 31)) & 1u)) continue;
+          const uint8_t* v = d.values.data() + (size_t)d.entry_size * (size_t)i;
+          if (d.data_type == PH_STRING) {
+            const size_t len = strnlen(reinterpret_cast<const char*>(v), d.entry_size);
+            var.i32((int32_t)len);
+            var.bytes(v, len);
+          } else {  // the value's bits, big-endian (ByteBuffer.putInt / putLong / putFloat / putDouble)
+            uint64_t x = 0;
+            memcpy(&x, v, d.entry_size);
+            if (d.entry_size == 4) var.i32((int32_t)(uint32_t)x);
+            else var.i64((int64_t)x);
+          }
+        }
+        put_be(dst, (uint32_t)start, 4);
+        // the length covers the serialised set only; the objectType int stands outside it, as for the HyperLogLog
+        // above (BaseDataTableBuilder.java:108-112, read back by DataTableImplV4.getCustomObject :292-300)
+        put_be(dst + 4, (uint32_t)(var.b.size() - start - 4), 4);
       } else {
         uint64_t v;
         memcpy(&v, base + (size_t)g * 8, 8);  // COUNT int64, SUM / MIN / MAX double bits

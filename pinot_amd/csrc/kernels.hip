@@ -29,6 +29,10 @@ void launch_scan(const KParams& p, int mode, int ng, int rec64, int grid, size_t
     return;
   }
   PH_HIP_CHECK(hipGetLastError());  // a failure left by an earlier unchecked call is reported as such, not as ours
+  if (p.num_dc) {  // DISTINCTCOUNT: the scan's bitset variant (the caller runs k_distinct_finish after its last launch)
+    launch_scan_distinct(p, mode, ng, grid, lds, s);
+    return;
+  }
   if (p.sk_list) {  // DISTINCTCOUNTHLL over star-tree sketch columns: the scan's sketch variant + the register merge
     launch_scan_sketch(p, mode, ng, grid, lds, s);
     return;

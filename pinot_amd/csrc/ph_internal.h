@@ -354,6 +354,17 @@ struct KParams {
   uint32_t sk_cap;                // entries sk_list holds
   unsigned long long* sk_list;    // [sk_cap] (document << 32 | row base); nullptr: no sketch slot
   uint32_t* sk_count;             // entries appended by the scan (zeroed again by the merge's launch)
+  // DISTINCTCOUNT bitsets (scan_distinct.hip; read by k_scan<.., LATE = 3> and k_distinct_finish only).  Row g of
+  // out_dc is dc_row_words words; slot h's bitset over its result dictionary is the dc_words[h] words at dc_off[h].
+  int32_t num_dc;                 // DISTINCTCOUNT slots (distinct columns); 0: the launch is not a DISTINCTCOUNT one
+  int32_t dc_lds;                 // MODE_AGG / MODE_GROUP_LDS: the workgroup's bitsets live in LDS at lds_dc_off
+  int32_t lds_dc_off;
+  int32_t dc_row_words;
+  int32_t dc_slot[kMaxHll];       // column slot of each DISTINCTCOUNT slot (its DevColumn::remap: dictId -> bit)
+  int32_t dc_off[kMaxHll];
+  int32_t dc_words[kMaxHll];      // ceil(result dictionary size / 32)
+  uint32_t* out_dc;               // [num_groups][dc_row_words]
+  int32_t* dc_counts;             // [num_groups][num_dc] popcounts, written by k_distinct_finish
 };
 
 // Kernel B of the partitioned group-by: aggregates one batch of records per partition in LDS, then merges
@@ -787,6 +798,10 @@ void launch_hll_table(const void* values, int32_t kind, int64_t n, int log2m, ui
 // scan_hll_sketch.hip: the generic scan's sketch variant (a launch whose KParams::sk_list is set) followed by
 // k_hll_sketch_merge over the list it appended
 void launch_scan_sketch(const KParams& p, int mode, int ng, int grid, size_t lds, hipStream_t s);
+// scan_distinct.hip: the generic scan's DISTINCTCOUNT variant (a launch whose KParams::num_dc is set), and
+// k_distinct_finish: the popcount of every (row, slot) bitset of out_dc into dc_counts, `rows` result rows
+void launch_scan_distinct(const KParams& p, int mode, int ng, int grid, size_t lds, hipStream_t s);
+void launch_distinct_finish(const KParams& p, int64_t rows, hipStream_t s);
 
 void build_bitmap_directory(Column& c);  // at pin, from c.inverted
 // at pin: the (key, slice) container directory of an exact range index's RangeBitmap (after Pinot's 12-byte header)
@@ -974,6 +989,16 @@ struct ph_result {
   std::vector<int32_t> agg_types;
   std::vector<int32_t> agg_log2m;
   std::vector<ResultBuf> aggs;   // per aggregation
+  // a DISTINCTCOUNT aggregation's rows are bitsets of `words` uint32 over its result dictionary: `count` values of
+  // `data_type`, laid out like group keys (entry_size bytes each), and the rows' popcounts (ph_result_distinct_*)
+  struct Distinct {
+    bool set = false;
+    int32_t data_type = 0, entry_size = 0, words = 0;
+    int64_t count = 0;
+    std::vector<uint8_t> values;
+    std::vector<int32_t> counts;
+  };
+  std::vector<Distinct> distinct;  // per aggregation (set only for DISTINCTCOUNT)
   int64_t num_groups = 0;
   int32_t mode = 0;
   ph_exec_stats stats{};

@@ -1162,7 +1162,11 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
   // segments a star-tree serves (GroupByPlanNode.java:77-99, AggregationPlanNode.java:122-141): their views, merged
   // with the rest (startree.cpp)
   const std::map<const ph_segment*, StarSegPlan>* star = dn ? dn->star : nullptr;
-  if (!star && !fds && !q->skip_star_tree && nseg > 0)
+  // (a query holding a DISTINCTCOUNT is not served from a tree: it scans the segments' own docs)
+  bool any_distinct = false;
+  for (int k = 0; k < q->num_aggregations && q->aggregations; ++k)
+    any_distinct |= q->aggregations[k].type == PH_AGG_DISTINCTCOUNT;
+  if (!star && !fds && !q->skip_star_tree && nseg > 0 && !any_distinct)
     if (ph_result* r = star_tree_execute(ctx, q, segs_in, nseg, dop)) return r;
   PH_HIP_CHECK(hipSetDevice(ctx->device));
   LaneGuard lane(ctx);  // this call's streams, events and staging (concurrent calls use their own)
@@ -1208,13 +1212,13 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
   const int nagg = q->num_aggregations;
   int log2m = 0;
   // value terms: a column, or a 2-operand expression `val_cols[j] <op> val_cols2[j]`
-  std::vector<std::string> val_cols, val_cols2, hll_cols;
+  std::vector<std::string> val_cols, val_cols2, hll_cols, dc_cols;
   std::vector<int> val_ops, val_exprs;
-  std::vector<int> agg_val(nagg, -1), agg_hll(nagg, -1);
+  std::vector<int> agg_val(nagg, -1), agg_hll(nagg, -1), agg_dc(nagg, -1);
   std::set<std::string> projected(group_cols.begin(), group_cols.end());
   for (int k = 0; k < nagg; ++k) {
     const ph_aggregation& a = q->aggregations[k];
-    if (a.type < PH_AGG_COUNT || a.type > PH_AGG_DISTINCTCOUNTHLL) fail(PH_ERR_UNSUPPORTED, "aggregation type");
+    if (a.type < PH_AGG_COUNT || a.type > PH_AGG_DISTINCTCOUNT) fail(PH_ERR_UNSUPPORTED, "aggregation type");
     res->agg_types.push_back(a.type);
     const int lm = a.type == PH_AGG_DISTINCTCOUNTHLL ? (a.log2m > 0 ? a.log2m : 8) : 0;
     res->agg_log2m.push_back(lm);
@@ -1233,6 +1237,19 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
         agg_hll[k] = (int)hll_cols.size() - 1;
       } else {
         agg_hll[k] = (int)(it - hll_cols.begin());
+      }
+      continue;
+    }
+    if (a.type == PH_AGG_DISTINCTCOUNT) {
+      // a bitset slot per distinct column (two DISTINCTCOUNTs of one column share it); log2m / column2 are ignored
+      if (a.expr_op != PH_EXPR_NONE) fail(PH_ERR_UNSUPPORTED, "DISTINCTCOUNT of an expression");
+      auto it = std::find(dc_cols.begin(), dc_cols.end(), std::string(a.column));
+      if (it == dc_cols.end()) {
+        if ((int)dc_cols.size() >= kMaxHll) fail(PH_ERR_UNSUPPORTED, "too many DISTINCTCOUNT columns");
+        dc_cols.push_back(a.column);
+        agg_dc[k] = (int)dc_cols.size() - 1;
+      } else {
+        agg_dc[k] = (int)(it - dc_cols.begin());
       }
       continue;
     }
@@ -1258,7 +1275,12 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
     agg_val[k] = j;
     val_ops[j] |= a.type == PH_AGG_SUM ? 1 : (a.type == PH_AGG_MIN ? 2 : 4);
   }
-  const int nvals = (int)val_cols.size(), num_hll = (int)hll_cols.size();
+  const int nvals = (int)val_cols.size(), num_hll = (int)hll_cols.size(), ndc = (int)dc_cols.size();
+  // DISTINCTCOUNT shapes the GPU path does not serve (the caller's CPU plan does)
+  if (ndc) {
+    if (dop) fail(PH_ERR_UNSUPPORTED, "DISTINCTCOUNT on dense partials");
+    if (star) fail(PH_ERR_UNSUPPORTED, "DISTINCTCOUNT over a star-tree view");
+  }
   if (q->filter_root >= 0)
     for (int i = 0; i < q->num_predicates; ++i) {
       if (!q->predicates[i].column) fail(PH_ERR_BAD_QUERY, "predicate without column");
@@ -1344,6 +1366,62 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
   }
   const int m = log2m ? (1 << log2m) : 0;
 
+  // the table-level dictionary of a column: ph_table_set_dictionary's, else the (cached) sorted value union of the
+  // queried segments' dictionaries -- group keys and DISTINCTCOUNT bitsets share ids across segments through it
+  auto column_dict = [&](const std::string& g) {
+    std::shared_ptr<GlobalDict> gd;
+    std::lock_guard<std::mutex> dlk(ctx->mu);  // table dictionaries / union cache
+    auto it = ctx->table_dicts.find(g);
+    if (it != ctx->table_dicts.end()) {
+      gd = it->second;
+    } else {
+      std::string key = g + "#";
+      for (auto* s : segs) key += std::to_string(s->id) + ",";
+      auto ct = ctx->union_cache.find(key);
+      if (ct != ctx->union_cache.end()) {
+        gd = ct->second;
+      } else {
+        gd = build_union(ctx, g, segs);
+        // bounded FIFO of unions; an evicted union's per-segment remaps go with it (segment_remap purges them)
+        while (ctx->union_cache.size() >= kUnionCacheEntries) {
+          ctx->union_cache.erase(ctx->union_order.front());
+          ctx->union_order.pop_front();
+        }
+        ctx->union_cache[key] = gd;
+        ctx->union_order.push_back(key);
+      }
+    }
+    return gd;
+  };
+  // DISTINCTCOUNT slots: each one's result dictionary and its place in a bitset row (KParams::dc_*)
+  std::vector<std::shared_ptr<GlobalDict>> dc_dicts;
+  std::vector<int64_t> dc_words(ndc, 0), dc_off(ndc, 0);
+  int64_t dc_row_words = 0;
+  for (int h = 0; h < ndc; ++h) {
+    if (segs.empty()) fail(PH_ERR_UNSUPPORTED, "DISTINCTCOUNT without segments");
+    dc_dicts.push_back(column_dict(dc_cols[h]));
+    dc_words[h] = std::max<int64_t>(1, (dc_dicts[h]->dict.size + 31) / 32);
+    dc_off[h] = dc_row_words;
+    dc_row_words += dc_words[h];
+  }
+  if (dc_row_words >= (int64_t(1) << 30)) fail(PH_ERR_UNSUPPORTED, "DISTINCTCOUNT dictionaries too large for one bitset row");
+  // the result columns of the DISTINCTCOUNT aggregations besides their bitset rows (ph_result_distinct_*)
+  auto init_distinct_results = [&]() {
+    res->distinct.assign(nagg, ph_result::Distinct{});
+    for (int k = 0; k < nagg; ++k) {
+      if (agg_dc[k] < 0) continue;
+      const Dictionary& d = dc_dicts[agg_dc[k]]->dict;
+      ph_result::Distinct& o = res->distinct[k];
+      o.set = true;
+      o.data_type = d.type;
+      o.entry_size = key_entry_size(d);
+      o.words = (int32_t)dc_words[agg_dc[k]];
+      o.count = d.size;
+      o.values.assign((size_t)o.entry_size * (size_t)d.size, 0);
+      for (int64_t i = 0; i < d.size; ++i) put_key_value(d, i, o.values.data() + (size_t)o.entry_size * i, o.entry_size);
+    }
+  };
+
   // ---- aggregation-only, no filter, metadata-answerable (NonScanBasedAggregationOperator)
   bool non_scan = q->filter_root < 0 && q->num_group_by == 0 && nagg > 0;
   for (int k = 0; k < nagg && non_scan; ++k) non_scan = q->aggregations[k].type != PH_AGG_SUM;
@@ -1354,7 +1432,13 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
     for (int k = 0; k < nagg; ++k) {
       const int t = q->aggregations[k].type;
       size_t w = t == PH_AGG_DISTINCTCOUNTHLL ? (size_t)(1 << res->agg_log2m[k]) : 8;
+      if (t == PH_AGG_DISTINCTCOUNT) w = 4 * (size_t)dc_words[agg_dc[k]];  // uint32[W] bitset rows
       res->aggs[k].assign(w * rows, 0);
+    }
+    if (ndc) {
+      init_distinct_results();
+      for (int k = 0; k < nagg; ++k)
+        if (agg_dc[k] >= 0) res->distinct[k].counts.assign((size_t)rows, 0);
     }
   };
   if (non_scan) {
@@ -1373,6 +1457,24 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
           v = a.type == PH_AGG_MIN ? std::min(v, x) : std::max(v, x);
         }
         memcpy(res->aggs[k].data(), &v, 8);
+      } else if (a.type == PH_AGG_DISTINCTCOUNT) {
+        // every value of every segment's dictionary (AggregationPlanNode.java:108-119: the dictionary-based operator)
+        const Dictionary& gd = dc_dicts[agg_dc[k]]->dict;
+        uint32_t* bits = reinterpret_cast<uint32_t*>(res->aggs[k].data());
+        for (auto* s : segs) {
+          const Column& c = *s->columns.at(a.column);
+          if (s->num_docs == 0) continue;
+          int64_t j = 0;
+          for (int32_t i = 0; i < c.cardinality; ++i) {
+            while (j < gd.size && gd.compare(j, c.dict, i) < 0) ++j;
+            if (j >= gd.size || gd.compare(j, c.dict, i) != 0)
+              fail(PH_ERR_INVALID_ARGUMENT, "table dictionary of column " + c.name + " does not contain a segment value");
+            bits[j >> 5] |= 1u << (j & 31);
+          }
+        }
+        int32_t n = 0;
+        for (int64_t w = 0; w < dc_words[agg_dc[k]]; ++w) n += __builtin_popcount(bits[w]);
+        res->distinct[k].counts[0] = n;
       } else {  // DISTINCTCOUNTHLL from the dictionaries
         uint8_t* regs = res->aggs[k].data();
         const int lm = res->agg_log2m[k];
@@ -1646,30 +1748,7 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
   std::vector<std::shared_ptr<GlobalDict>> gdicts;
   int64_t num_groups = 1;
   for (auto& g : group_cols) {
-    std::shared_ptr<GlobalDict> gd;
-    std::lock_guard<std::mutex> dlk(ctx->mu);  // table dictionaries / union cache
-    auto it = ctx->table_dicts.find(g);
-    if (dn && dn->dicts) {
-      gd = (*dn->dicts).at(gdicts.size());
-    } else if (it != ctx->table_dicts.end()) {
-      gd = it->second;
-    } else {
-      std::string key = g + "#";
-      for (auto* s : segs) key += std::to_string(s->id) + ",";
-      auto ct = ctx->union_cache.find(key);
-      if (ct != ctx->union_cache.end()) {
-        gd = ct->second;
-      } else {
-        gd = build_union(ctx, g, segs);
-        // bounded FIFO of unions; an evicted union's per-segment remaps go with it (segment_remap purges them)
-        while (ctx->union_cache.size() >= kUnionCacheEntries) {
-          ctx->union_cache.erase(ctx->union_order.front());
-          ctx->union_order.pop_front();
-        }
-        ctx->union_cache[key] = gd;
-        ctx->union_order.push_back(key);
-      }
-    }
+    std::shared_ptr<GlobalDict> gd = (dn && dn->dicts) ? (*dn->dicts).at(gdicts.size()) : column_dict(g);
     gdicts.push_back(gd);
     const int64_t sz = std::max<int64_t>(1, gd->dict.size);
     // mixed-radix keys stay below 2^62 (int64 and never the hash table's empty marker)
@@ -1753,6 +1832,13 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
     kp.hll_slot[h] = pl.slot.at(hll_cols[h]);
     kp.hll_words[h] = hll_words[h];
   }
+  kp.num_dc = ndc;
+  kp.dc_row_words = (int32_t)dc_row_words;
+  for (int h = 0; h < ndc; ++h) {
+    kp.dc_slot[h] = pl.slot.at(dc_cols[h]);
+    kp.dc_off[h] = (int32_t)dc_off[h];
+    kp.dc_words[h] = (int32_t)dc_words[h];
+  }
 
   // packed streams of the hot loop: slot 0 = the single-leaf filter column of each segment (if any),
   // then the group-by columns, then the aggregated value columns; all of them are LDS-staged.
@@ -1829,7 +1915,7 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
   float dev_ms = 0.f;
   // a plain group-by's scan completion, matched-doc count and limit flags are read at the compaction's sync
   // (one host round trip instead of three)
-  const bool defer_sync = q->num_group_by > 0 && num_hll == 0 && dop != DENSE_EXECUTE && !fin;
+  const bool defer_sync = q->num_group_by > 0 && num_hll == 0 && ndc == 0 && dop != DENSE_EXECUTE && !fin;
   std::unique_ptr<PinnedBlock> dsc;  // pinned: matched total, then 3 words per limit segment
   // the fused AND walks' sums (pinned, stream b): read at the end of the call, so the result compaction and copies
   // on the main stream overlap the walks instead of waiting behind them
@@ -1871,12 +1957,26 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
   stamp("kparams");
   // ---- mode selection (LDS table offsets are relative to the end of the staging areas, fixed below)
   size_t lds_tables = 16;
+  size_t lds_tables_no_dc = 16;  // MODE_AGG: the tables without the DISTINCTCOUNT bitsets (the HBM form's)
   int rec64 = 0;
   kp.stage_off = 0;
   if (q->num_group_by == 0) {
-    mode = (nvals == 0 && num_hll == 0) ? MODE_COUNT : MODE_AGG;
+    mode = (nvals == 0 && num_hll == 0 && ndc == 0) ? MODE_COUNT : MODE_AGG;
     kp.lds_hll_off = 0;
     lds_tables = (size_t)num_hll * (m ? m : 1) * 4 + 16;
+    lds_tables_no_dc = lds_tables;
+    if (ndc) {
+      // the one row of DISTINCTCOUNT bitsets in LDS when it fits beside the HLL registers under the LDS table bound
+      // (option lds_table_max forces the HBM form), else straight in HBM
+      size_t dc_max = 64 * 1024;
+      if (ctx->has(OPT_LDS_TABLE_MAX)) dc_max = (size_t)std::max<int64_t>(0, ctx->opt(OPT_LDS_TABLE_MAX));
+      const size_t off = (lds_tables + 15) / 16 * 16;
+      if (off + (size_t)dc_row_words * 4 <= dc_max) {
+        kp.dc_lds = 1;
+        kp.lds_dc_off = (int32_t)off;
+        lds_tables = off + (size_t)dc_row_words * 4;
+      }
+    }
   } else {
     kp.lds_cnt_off = 0;
     size_t off = G < (int64_t(1) << 24) ? ((size_t)G * 4 + 15) / 16 * 16 : SIZE_MAX / 2;
@@ -1892,7 +1992,13 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
     }
     kp.lds_hll_off = (int32_t)std::min<size_t>(off, INT32_MAX);
     off += (size_t)G * num_hll * (m ? m : 1) * 4;
-    const bool part_ok = num_hll == 0 && nvals <= 1 && (nvals == 0 || (val_is_int[0] && !val_exprs[0] && vmax >= vmin &&
+    if (ndc) {  // the DISTINCTCOUNT bitset rows after the HLL registers, under the same bound
+      off = off < SIZE_MAX / 4 ? (off + 15) / 16 * 16 : off;
+      kp.lds_dc_off = (int32_t)std::min<size_t>(off, INT32_MAX);
+      const double dcb = (double)G * (double)dc_row_words * 4.0;
+      off = (dcb < 1e12 && off < SIZE_MAX / 4) ? off + (size_t)dcb : SIZE_MAX / 2;
+    }
+    const bool part_ok = num_hll == 0 && ndc == 0 && nvals <= 1 && (nvals == 0 || (val_is_int[0] && !val_exprs[0] && vmax >= vmin &&
                                                                        (uint64_t)(vmax - vmin) < (1ull << 32))) &&
                          G <= ((int64_t)kPartMaxParts << kPartKeysLog2) && !any_limit &&
                          !ctx->has(OPT_DISABLE_PARTITION);
@@ -1903,17 +2009,30 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
     // (38.8 vs 1.7 ms: the cache cannot hold every key, the rest pays device atomics)
     size_t lds_table_max = 64 * 1024;
     if (ctx->has(OPT_LDS_TABLE_MAX)) lds_table_max = (size_t)std::max<int64_t>(0, ctx->opt(OPT_LDS_TABLE_MAX));
-    const bool cache_ok = num_hll == 0 && nvals <= 1 && !ctx->has(OPT_NO_GROUP_CACHE);
+    const bool cache_ok = num_hll == 0 && ndc == 0 && nvals <= 1 && !ctx->has(OPT_NO_GROUP_CACHE);
     // (an explicit lds_table_max holds for every query: tests force the HBM table of a DISTINCTCOUNTHLL group-by)
     if (off <= ((cache_ok || ctx->has(OPT_LDS_TABLE_MAX)) ? lds_table_max : (size_t)64 * 1024)) {
       mode = MODE_GROUP_LDS;
       lds_tables = off;
+      kp.dc_lds = ndc > 0;
     } else if (part_ok && G >= 65536) {
       mode = MODE_PARTITION;
     } else {
       int nout = 1;  // 8-byte tables per group
       for (int j = 0; j < nvals; ++j) nout += __builtin_popcount(val_ops[j] & 7);
       const double bytes = (double)G * (8.0 * nout + 4.0 * num_hll * (m ? m : 1));
+      if (ndc) {
+        // DISTINCTCOUNT runs on the dense tables only (no hash table of bitset rows).  Its budget counts the device
+        // table and the host copy of the rows that can be non-empty: at most one per scanned doc
+        if (bytes > kDenseTableBudget)
+          fail(PH_ERR_UNSUPPORTED, "DISTINCTCOUNT over a group key space beyond the dense tables");
+        int64_t live_docs = 0;
+        for (int i = 0; i < nseg; ++i)
+          if (seg_live[i]) live_docs += segs[i]->num_docs;
+        const double row_bytes = 4.0 * (double)dc_row_words;
+        if (bytes + (double)G * row_bytes + (double)std::min<int64_t>(G, live_docs) * row_bytes > kDenseTableBudget)
+          fail(PH_ERR_UNSUPPORTED, "DISTINCTCOUNT bitset table exceeds the dense table budget");
+      }
       if (bytes <= kDenseTableBudget) {
         mode = MODE_GROUP_GLOBAL;
         // per-workgroup LDS cache of the groups it meets (open addressing, 1024 slots): repeated keys aggregate in
@@ -1965,6 +2084,7 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
   };
   int tix = 0;
   const int64_t hll_table_words = TR * num_hll * (m ? m : 1);
+  const int64_t dc_table_words = TR * dc_row_words;
   kp.out_count = reinterpret_cast<unsigned long long*>(out_table(tix, 8 * (size_t)TR));
   for (int j = 0; j < nvals; ++j) {
     if (val_ops[j] & 1) kp.out_sum[j] = out_table(tix, 8 * (size_t)TR);
@@ -1976,6 +2096,10 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
     kp.hkeys = hkeys;
   }
   if (num_hll) kp.out_hll = reinterpret_cast<uint32_t*>(out_table(tix, 4 * (size_t)hll_table_words));
+  if (ndc) {
+    kp.out_dc = scratch.alloc<uint32_t>((size_t)dc_table_words);
+    kp.dc_counts = scratch.alloc<int32_t>((size_t)TR * ndc);
+  }
   // identities of every output table (again before a numGroupsLimit rescan)
   auto init_tables = [&]() {
     PH_HIP_CHECK(hipMemsetAsync(kp.out_count, 0, sizeof(unsigned long long) * TR, st));
@@ -1986,6 +2110,10 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
     }
     if (hkeys) PH_HIP_CHECK(hipMemsetAsync(hkeys, 0xFF, 8 * TR, st));  // kHashEmpty
     if (num_hll) PH_HIP_CHECK(hipMemsetAsync(kp.out_hll, 0, 4 * hll_table_words, st));
+    if (ndc) {  // the scan's inserts only set bits: the table starts from zero, on the scan's stream
+      PH_HIP_CHECK(hipMemsetAsync(kp.out_dc, 0, 4 * (size_t)dc_table_words, st));
+      PH_HIP_CHECK(hipMemsetAsync(kp.dc_counts, 0, 4 * (size_t)TR * ndc, st));
+    }
   };
   init_tables();
 
@@ -2009,7 +2137,7 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
   // leaves' densities multiplied: an independence estimate) -> gather the matched docs instead of streaming every
   // referenced column
   bool sparse_plan = false;
-  if ((mode == MODE_GROUP_LDS || mode == MODE_GROUP_GLOBAL) && num_hll == 0 && nvals <= 1 && q->num_group_by > 0) {
+  if ((mode == MODE_GROUP_LDS || mode == MODE_GROUP_GLOBAL) && num_hll == 0 && ndc == 0 && nvals <= 1 && q->num_group_by > 0) {
     bool ok = true;
     double docs = 0, hits = 0;
     for (int i = 0; i < nseg && ok; ++i) {
@@ -2039,7 +2167,7 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
   // k_agg_sparse over ANDs of scan leaves only (register-direct leaves, then gathers of the matched docs' values):
   // aggregation-only queries whose every segment's AND keeps < 1/8 of the docs (same estimate as above)
   bool agg_conj = false;
-  if (mode == MODE_AGG && nvals >= 1 && (nvals == 1 || std::none_of(val_exprs.begin(), val_exprs.end(), [](int x) { return x != 0; }))) {
+  if (mode == MODE_AGG && ndc == 0 && nvals >= 1 && (nvals == 1 || std::none_of(val_exprs.begin(), val_exprs.end(), [](int x) { return x != 0; }))) {
     bool ok = true;
     double docs = 0, hits = 0;
     for (int i = 0; i < nseg && ok; ++i) {
@@ -2188,6 +2316,10 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
     }
     for (int g = 0; g < q->num_group_by; ++g)
       d.cols[kp.group_slot[g]].remap = segment_remap(ctx, *s, *s->columns.at(group_cols[g]), *gdicts[g]);
+    // DISTINCTCOUNT: dictId -> bit of the slot's result dictionary (a column that is also a group-by column has the
+    // same dictionary, so the same remap)
+    for (int h = 0; h < ndc; ++h)
+      d.cols[kp.dc_slot[h]].remap = segment_remap(ctx, *s, *s->columns.at(dc_cols[h]), *dc_dicts[h]);
     for (int h = 0; h < num_hll; ++h) {
       Column& hc = *s->columns.at(hll_cols[h]);
       if (hll_words[h]) {
@@ -2262,7 +2394,7 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
     }
     agg_sparse_plan = (all_bitmap_agg && hits * 8 < docs) || agg_conj;
     if (ctx->has(OPT_AGG_SPARSE)) agg_sparse_plan = (all_bitmap_agg || agg_conj) && ctx->opt(OPT_AGG_SPARSE) != 0;
-    if (any_sketch) agg_sparse_plan = false;
+    if (any_sketch || ndc) agg_sparse_plan = false;  // (DISTINCTCOUNT bitsets: the generic scan only)
   }
   const bool agg_cont_plan = cont_defer && agg_sparse_plan && all_bitmap_agg && !agg_conj;
   int64_t chunk_docs_total = 0;  // the streaming chunk list's words x 64 and its widest chunk
@@ -2317,6 +2449,17 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
       while (tw > 4 && stage(tw) + lds_tables > 160 * 1024) tw /= 2;
       if (stage(tw) + lds_tables > 160 * 1024) fail(PH_ERR_UNSUPPORTED, "LDS group table and staging exceed 160 KiB");
     }
+    if (mode == MODE_AGG && kp.dc_lds) {
+      // an lds_table_max above the default can admit a bitset row that does not fit beside the staging areas in one
+      // CU's 160 KiB: the HBM form then (the tile stays as every other MODE_AGG query's)
+      size_t b = 0;
+      for (int s2 = 0; s2 < kp.nstage; ++s2) b += maxbits[s2] ? stage_stream_bytes(tw, maxbits[s2]) : 0;
+      if ((size_t)kWaves * std::max<size_t>(16, b) + lds_tables > 160 * 1024) {
+        kp.dc_lds = 0;
+        kp.lds_dc_off = 0;
+        lds_tables = lds_tables_no_dc;
+      }
+    }
     if (loads(tw) > pool) fail(PH_ERR_UNSUPPORTED, "staged streams too wide for the prefetch pool");
     kp.tile_words = tw;
     int32_t soff = 0;
@@ -2329,7 +2472,7 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
   // a decode that gathers (bitset / bitmap / program filters, key remaps, dictionary values, HLL tables)
   // would wait behind an early prefetch
   for (auto& d : dsegs) {
-    bool g = d.fkind == FK_SET || d.fkind == FK_BITMAP || d.fkind == FK_GENERIC || num_hll > 0;
+    bool g = d.fkind == FK_SET || d.fkind == FK_BITMAP || d.fkind == FK_GENERIC || num_hll > 0 || ndc > 0;
     for (int k = 0; d.fkind == FK_CONJ && k < d.nconj; ++k) g |= d.cset[k] != nullptr || d.clen[k] == 0;
     for (int gi = 0; gi < q->num_group_by; ++gi) g |= d.cols[kp.group_slot[gi]].remap != nullptr;
     for (int j = 0; j < nvals; ++j) g |= d.vals[j].kind != VK_PACKED || (val_exprs[j] && d.vals2[j].kind != VK_PACKED);
@@ -2391,7 +2534,7 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
   // leaves; its 32-bit tile sums need value offsets below 2^26
   //   r3: also FK_CONJ ANDs of range leaves (no applyAnd statistic to count) and integer 2-operand value terms of
   //   two packed columns (per-doc int64 fold; SSB Q1.x)
-  kp.agg_fast = mode == MODE_AGG && nvals == 1 && num_hll == 0 && val_is_int[0] && !kp.late_prefetch &&
+  kp.agg_fast = mode == MODE_AGG && nvals == 1 && num_hll == 0 && ndc == 0 && val_is_int[0] && !kp.late_prefetch &&
                 !ctx->has(OPT_AGG_GENERIC);
   for (auto& d : dsegs) {
     if (!kp.agg_fast) break;  // (val_exprs is empty without value columns)
@@ -2404,7 +2547,7 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
   }
   // the lean LDS group-by (k_group_lds_lean): identity remaps, at most one packed integer value column whose
   // offsets from the table-wide minimum fit 32 bits, ALL / RANGE / DOCRANGE leaves
-  kp.lds_fast = mode == MODE_GROUP_LDS && num_hll == 0 && nvals <= 1 && !kp.late_prefetch &&
+  kp.lds_fast = mode == MODE_GROUP_LDS && num_hll == 0 && ndc == 0 && nvals <= 1 && !kp.late_prefetch &&
                 !ctx->has(OPT_LDS_GENERIC);
   if (nvals == 1)
     kp.lds_fast = kp.lds_fast && val_is_int[0] && !val_exprs[0] && vmax >= vmin && (uint64_t)(vmax - vmin) < (1ull << 32);
@@ -2474,6 +2617,7 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
     kp.stage_off = 0;
     kp.lds_cnt_off += (int32_t)stage_bytes;
     kp.lds_hll_off += (int32_t)stage_bytes;
+    kp.lds_dc_off += (int32_t)stage_bytes;
     kp.gc_key_off += (int32_t)stage_bytes;
     for (int j = 0; j < nvals; ++j) {
       kp.lds_sum_off[j] += (int32_t)stage_bytes;
@@ -2790,6 +2934,7 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
                           : kp.group_sparse ? PH_KERNEL_GROUP_SPARSE
                           : kp.group_reg  ? PH_KERNEL_GROUP_REG
                           : kp.lds_fast  ? PH_KERNEL_GROUP_LDS_LEAN
+                          : ndc          ? (kp.dc_lds ? PH_KERNEL_SCAN_DISTINCT_LDS : PH_KERNEL_SCAN_DISTINCT_HBM)
                                          : PH_KERNEL_SCAN;
       // device_ms opens here: it covers the numGroupsLimit pass and (below) the bitmap build too
       PH_HIP_CHECK(hipEventRecord(lane.lane->ev_start, st));
@@ -2934,6 +3079,7 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
                             st);
       }
       if (!scanned) run_scan(kp);
+      if (ndc) launch_distinct_finish(kp, TR, st);  // the rows' popcounts, behind the last scan launch
       PH_HIP_CHECK(hipEventRecord(lane.lane->ev_stop, st));
     } else {
       // ---- partitioned group-by: batches of chunks; kernel A (filter + decode + partition) on `st`,
@@ -3466,6 +3612,7 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
       at[k] = need;
       const int t = q->aggregations[k].type;
       need += t == PH_AGG_COUNT ? 0 : (t == PH_AGG_DISTINCTCOUNTHLL ? 4 * (size_t)m : 8);
+      if (t == PH_AGG_DISTINCTCOUNT) need += 4 * (size_t)dc_words[agg_dc[k]];  // the bitset, then its count (8 bytes)
     }
     PinnedBlock blk_hold(ctx, st, need);
     uint8_t* blk = blk_hold.as<uint8_t>();
@@ -3474,7 +3621,11 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
       const int t = q->aggregations[k].type;
       if (t == PH_AGG_DISTINCTCOUNTHLL)
         PH_HIP_CHECK(hipMemcpyAsync(blk + at[k], kp.out_hll + (size_t)agg_hll[k] * m, 4 * m, hipMemcpyDeviceToHost, st));
-      else if (t != PH_AGG_COUNT)
+      else if (t == PH_AGG_DISTINCTCOUNT) {
+        const int h = agg_dc[k];
+        PH_HIP_CHECK(hipMemcpyAsync(blk + at[k], kp.out_dc + dc_off[h], 4 * (size_t)dc_words[h], hipMemcpyDeviceToHost, st));
+        PH_HIP_CHECK(hipMemcpyAsync(blk + at[k] + 4 * (size_t)dc_words[h], kp.dc_counts + h, 4, hipMemcpyDeviceToHost, st));
+      } else if (t != PH_AGG_COUNT)
         PH_HIP_CHECK(hipMemcpyAsync(blk + at[k], src_of(k), 8, hipMemcpyDeviceToHost, st));
     }
     PH_HIP_CHECK(hipStreamSynchronize(st));
@@ -3491,6 +3642,10 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
       } else if (t == PH_AGG_DISTINCTCOUNTHLL) {
         const uint32_t* r = reinterpret_cast<const uint32_t*>(blk + at[k]);
         for (int j = 0; j < m; ++j) dst[j] = (uint8_t)r[j];
+      } else if (t == PH_AGG_DISTINCTCOUNT) {
+        const size_t wb = 4 * (size_t)dc_words[agg_dc[k]];
+        memcpy(dst, blk + at[k], wb);
+        memcpy(res->distinct[k].counts.data(), blk + at[k] + wb, 4);
       } else {
         int64_t raw;
         memcpy(&raw, blk + at[k], 8);
@@ -3499,7 +3654,7 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
       }
     }
 
-  } else if (num_hll == 0) {
+  } else if (num_hll == 0 && ndc == 0) {
     // device-side compaction: non-empty groups in key order, keys decoded, values converted to double,
     // copied straight into pinned result columns
     CompactParams cp{};
@@ -3617,7 +3772,7 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
       string_ids[g].pinned = nullptr;
     }
   } else {
-    // group-by with DISTINCTCOUNTHLL registers: host-side materialisation (MODE_GROUP_HASH: rows are the occupied
+    // group-by with DISTINCTCOUNTHLL registers or DISTINCTCOUNT bitsets: host-side materialisation (MODE_GROUP_HASH: rows are the occupied
     // slots, ordered by their raw key like the dense tables' rows)
     std::vector<unsigned long long> cnt(RG);
     PH_HIP_CHECK(hipMemcpy(cnt.data(), kp.out_count, 8 * RG, hipMemcpyDeviceToHost));
@@ -3642,6 +3797,7 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
     init_row_results(R);
     std::map<void*, std::vector<int64_t>> fetched;
     std::vector<uint32_t> regs;
+    std::vector<int32_t> dcnt;  // [RG][ndc] DISTINCTCOUNT popcounts (k_distinct_finish)
     for (int k = 0; k < nagg; ++k) {
       const int t = q->aggregations[k].type;
       uint8_t* dst = res->aggs[k].data();
@@ -3658,6 +3814,33 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
         for (int64_t r = 0; r < R; ++r)
           for (int j = 0; j < m; ++j)
             dst[(size_t)r * m + j] = (uint8_t)regs[((size_t)live[r] * num_hll + agg_hll[k]) * m + j];
+      } else if (t == PH_AGG_DISTINCTCOUNT) {
+        // the non-empty rows' bitsets and device-computed counts, the table read in slabs of rows (<= 64 MiB each):
+        // one walk over the table at the first DISTINCTCOUNT fills every DISTINCTCOUNT aggregation of the query
+        if (!dcnt.empty()) continue;
+        dcnt.resize((size_t)RG * ndc);
+        PH_HIP_CHECK(hipMemcpy(dcnt.data(), kp.dc_counts, 4 * dcnt.size(), hipMemcpyDeviceToHost));
+        const size_t RW = (size_t)dc_row_words;
+        const int64_t slab_rows = std::max<int64_t>(1, (int64_t)((size_t(64) << 20) / (4 * RW)));
+        std::vector<uint32_t> slab;
+        // (dense tables only, no MODE_GROUP_HASH: `live` ascends in table rows, so the slabs only move forward)
+        int64_t s0 = -1;
+        for (int64_t r = 0; r < R; ++r) {
+          const int64_t g = live[r];
+          if (s0 < 0 || g >= s0 + slab_rows) {
+            s0 = g;
+            const int64_t nr = std::min<int64_t>(slab_rows, RG - s0);
+            slab.resize((size_t)nr * RW);
+            PH_HIP_CHECK(hipMemcpy(slab.data(), kp.out_dc + (size_t)s0 * RW, 4 * slab.size(), hipMemcpyDeviceToHost));
+          }
+          for (int k2 = k; k2 < nagg; ++k2) {
+            if (q->aggregations[k2].type != PH_AGG_DISTINCTCOUNT) continue;
+            const int h = agg_dc[k2];
+            const size_t W = (size_t)dc_words[h];
+            memcpy(res->aggs[k2].data() + 4 * W * (size_t)r, slab.data() + (size_t)(g - s0) * RW + dc_off[h], 4 * W);
+            res->distinct[k2].counts[(size_t)r] = dcnt[(size_t)g * ndc + h];
+          }
+        }
       } else {
         void* src = src_of(k);
         auto& buf = fetched[src];

@@ -468,6 +468,63 @@ struct ScanAcc {
   double dsum[kMaxVals];
 };
 
+// ------------------------------------------------------------------ DISTINCTCOUNT bitsets (k_scan<.., LATE = 3>)
+// The reference keeps a RoaringBitmap of dictIds per result holder (BaseDistinctAggregateAggregationFunction.java:
+// 133-168); here a result row holds, per DISTINCTCOUNT slot h, a bitset over the slot's result dictionary: row g is
+// words [g * dc_row_words, (g + 1) * dc_row_words) of the table, slot h's dc_words[h] words start at dc_off[h], and
+// value i of the dictionary is bit i & 31 of word i >> 5.  The table lives in LDS (KParams::dc_lds: MODE_AGG when it
+// fits, MODE_GROUP_LDS always; flushed once per workgroup) or in HBM.  Every atomic is a no-return OR behind a read:
+// a value already present -- the hot value of a skewed column above all -- costs a load, not an atomic.
+__device__ __forceinline__ uint32_t* distinct_lds(const KParams& p, uint8_t* smem) {
+  return reinterpret_cast<uint32_t*>(smem + p.lds_dc_off);
+}
+
+template <int MODE>
+__device__ __forceinline__ void distinct_insert(const KParams& p, SegPtr S, uint8_t* smem, uint32_t doc, int64_t g) {
+#pragma unroll
+  for (int h = 0; h < kMaxHll; ++h) {
+    if (h >= p.num_dc) continue;
+    ColRef col = S->cols[p.dc_slot[h]];
+    uint32_t id = unpack_col(col, doc);
+    if (col.remap) id = (uint32_t)gld(col.remap + id);  // dictId -> result dictionary (nullptr: they are equal)
+    const int64_t wi = g * p.dc_row_words + p.dc_off[h] + (int64_t)(id >> 5);
+    const uint32_t bit = 1u << (id & 31u);
+    if (MODE != MODE_GROUP_GLOBAL && p.dc_lds) {
+      uint32_t* w = distinct_lds(p, smem) + wi;
+      if (!(*w & bit)) (void)__hip_atomic_fetch_or(w, bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    } else {
+      // Test before set.  The load is a device-scope atomic load (served by L2, where the ORs land), the table was
+      // zeroed by a memset ordered before the launch on its stream and bits only go 0 -> 1 within a launch: what the
+      // load returns can lag the table only by showing a bit still clear, and then the OR below is issued -- setting a
+      // set bit again changes nothing.  It can never show a bit that is not set.
+      uint32_t* w = p.out_dc + wi;
+      if (!(__hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & bit))
+        (void)__hip_atomic_fetch_or(w, bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+}
+
+// the workgroup's LDS bitsets: zeroed before the scan (followed by the kernel's barrier) ...
+template <int MODE>
+__device__ __forceinline__ void distinct_lds_clear(const KParams& p, uint8_t* smem) {
+  if (MODE == MODE_GROUP_GLOBAL || !p.dc_lds) return;
+  const int64_t n = (MODE == MODE_GROUP_LDS ? p.num_groups : 1) * p.dc_row_words;
+  uint32_t* t = distinct_lds(p, smem);
+  for (int64_t i = threadIdx.x; i < n; i += kBlock) t[i] = 0;
+}
+// ... and ORed into the HBM table after it: non-zero words only, no value returned (the flush shape of lds_hll)
+template <int MODE>
+__device__ __forceinline__ void distinct_lds_flush(const KParams& p, uint8_t* smem) {
+  if (MODE == MODE_GROUP_GLOBAL || !p.dc_lds) return;
+  __syncthreads();
+  const int64_t n = (MODE == MODE_GROUP_LDS ? p.num_groups : 1) * p.dc_row_words;
+  const uint32_t* t = distinct_lds(p, smem);
+  for (int64_t i = threadIdx.x; i < n; i += kBlock) {
+    const uint32_t x = t[i];
+    if (x) (void)__hip_atomic_fetch_or(p.out_dc + i, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
 // One staged tile of one segment: every parameter the inner loop needs is hoisted into (scalar) registers
 // once per tile, and the filter kind is a template parameter, so the per-64-doc body is LDS reads + ALU.
 template <int MODE, int NG, int REC64, int FK, int LATE>
@@ -734,6 +791,8 @@ __device__ __forceinline__ void process_tile(const KParams& p, SegPtr S, uint8_t
         if (MODE == MODE_GROUP_GLOBAL || MODE == MODE_GROUP_HASH) atomicMax(&p.out_hll[ri], e & 0xffu);  // g: slot
         else atomicMax(&lds_hll[ri], e & 0xffu);
       }
+      // DISTINCTCOUNT (scan_distinct.hip): only LATE == 3 carries the insert
+      if constexpr (LATE == 3) distinct_insert<MODE>(p, S, smem, doc, g);
     }
   };
 
@@ -840,7 +899,8 @@ __device__ __forceinline__ void process_tile(const KParams& p, SegPtr S, uint8_t
 
 // LATE: 0 = the next tile's loads are issued before this tile's decode, 1 = after it (a decode that gathers), 2 = 1
 // with DISTINCTCOUNTHLL slots that read star-tree sketch columns (scan_hll_sketch.hip; only sketch queries
-// instantiate it, so no other query carries the append).
+// instantiate it, so no other query carries the append), 3 = 1 with DISTINCTCOUNT bitset slots (scan_distinct.hip; only
+// DISTINCTCOUNT queries instantiate it, so no other query carries the insert, the LDS clear or the flush).
 // Persistent grid over the chunk list.  A chunk (<= 256 words of one segment) is processed in rounds: in
 // round r wave w takes tile r * kWaves + w.  Rounds are workgroup-uniform (MODE_PARTITION flushes at round
 // boundaries with workgroup barriers); the other modes never synchronise inside the loop.
@@ -896,6 +956,7 @@ __global__ void __launch_bounds__(MODE == MODE_PARTITION ? kPartBlock : kBlock) 
     uint32_t* words = reinterpret_cast<uint32_t*>(smem + p.pl_lcnt_off);
     for (int i = threadIdx.x; i < p.num_parts; i += BLOCK) words[i] = 0;
   }
+  if constexpr (LATE == 3) distinct_lds_clear<MODE>(p, smem);
   __syncthreads();
 
   ScanAcc acc;
@@ -1085,6 +1146,7 @@ __global__ void __launch_bounds__(MODE == MODE_PARTITION ? kPartBlock : kBlock) 
       }
     }
   }
+  if constexpr (LATE == 3) distinct_lds_flush<MODE>(p, smem);
   __syncthreads();
   if (threadIdx.x == 0 && s_matched && (MODE == MODE_COUNT || MODE == MODE_AGG))
     atomicAdd(&p.out_count[0], s_matched);

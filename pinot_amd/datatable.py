@@ -6,7 +6,7 @@ dictionary, DataSchema.fromBytes, fixed-size rows, variable-size data, metadata 
 ``reduce_datatables`` is the broker's merge of several servers' tables for this path:
 GroupByDataTableReducer.reduceAndSetResults (core/query/reduce/GroupByDataTableReducer.java:99) /
 AggregationDataTableReducer -- intermediate results merged per group key with AggregationFunction.merge
-(COUNT / SUM add, MIN / MAX, DISTINCTCOUNTHLL HyperLogLog.addAll = register max), then the final results, ORDER BY
+(COUNT / SUM add, MIN / MAX, DISTINCTCOUNTHLL HyperLogLog.addAll = register max, DISTINCTCOUNT set union), then the final results, ORDER BY
 and LIMIT (pinot_amd.reduce.reduce_groups).
 """
 from __future__ import annotations
@@ -17,8 +17,8 @@ from typing import Any, Dict, List, Sequence
 
 import numpy as np
 
-from .query import COUNT, DISTINCTCOUNTHLL, MAX, MIN, SUM, QueryContext
-from .reduce import ResultTable, reduce_groups
+from .query import COUNT, DISTINCTCOUNT, DISTINCTCOUNTHLL, MAX, MIN, SUM, QueryContext
+from .reduce import ResultTable, merge_intermediate, reduce_groups
 
 # MetadataKey id -> (name, value type) (DataTable.java:103-137); "I" int, "L" long, "S" string
 METADATA_KEYS = {1: ("table", "S"), 2: ("numDocsScanned", "L"), 3: ("numEntriesScannedInFilter", "L"),
@@ -36,6 +36,8 @@ METADATA_KEYS = {1: ("table", "S"), 2: ("numDocsScanned", "L"), 3: ("numEntriesS
                  30: ("operatorExecutionTimeMs", "L"), 31: ("operatorId", "S"), 32: ("operatorExecStartTimeMs", "L"),
                  33: ("operatorExecEndTimeMs", "L")}
 HLL_OBJECT_TYPE = 6  # ObjectSerDeUtils.ObjectType.HyperLogLog
+# the value sets of DISTINCTCOUNT by stored type (ObjectSerDeUtils.java:113-123)
+SET_OBJECT_TYPES = {9: "INT", 15: "LONG", 16: "FLOAT", 17: "DOUBLE", 18: "STRING"}
 
 
 @dataclass
@@ -45,6 +47,10 @@ class DataTable:
     rows: List[List[Any]]
     metadata: Dict[str, str] = field(default_factory=dict)
     exceptions: Dict[int, str] = field(default_factory=dict)
+    # framing of the variable-size section: its length and every OBJECT cell's (offset, length) in row order -- the
+    # length excludes the cell's leading objectType int (BaseDataTableBuilder.java:108-112)
+    variable_size: int = 0
+    object_spans: List[tuple] = field(default_factory=list)
 
 
 class _Reader:
@@ -79,6 +85,31 @@ def hll_deserialize(b: bytes):
     return log2m, regs.astype(np.uint8)
 
 
+def set_deserialize(otype: int, b: bytes) -> frozenset:
+    """A DISTINCTCOUNT value set from ObjectSerDeUtils bytes (IntSet / LongSet / FloatSet / DoubleSet / StringSet
+    deserializers, ObjectSerDeUtils.java:725-891): int32 BE size, then the values in any order."""
+    data_type = SET_OBJECT_TYPES[otype]
+    n = struct.unpack_from(">i", b, 0)[0]
+    if n < 0:
+        raise ValueError(f"{data_type} set of size {n}")
+    if data_type == "STRING":
+        out, p = [], 4
+        for _ in range(n):
+            ln = struct.unpack_from(">i", b, p)[0]
+            if ln < 0 or p + 4 + ln > len(b):
+                raise ValueError(f"StringSet record of {ln} bytes at {p} runs past the object's {len(b)} bytes")
+            out.append(bytes(b[p + 4:p + 4 + ln]).decode("utf-8"))
+            p += 4 + ln
+    else:
+        dt = {"INT": ">i4", "LONG": ">i8", "FLOAT": ">f4", "DOUBLE": ">f8"}[data_type]
+        p = 4 + n * np.dtype(dt).itemsize
+        out = np.frombuffer(b, dt, n, 4).tolist() if p <= len(b) else []
+    # the object's length is exactly its serialisation's (the reader slices it to that: DataTableImplV4.java:292-300)
+    if p != len(b):
+        raise ValueError(f"{data_type} set of {n} values takes {p} bytes, the object has {len(b)}")
+    return frozenset(out)
+
+
 def decode(buf: bytes) -> DataTable:
     r = _Reader(buf)
     version = r.i32()
@@ -107,7 +138,7 @@ def decode(buf: bytes) -> DataTable:
         row += width.get(t, 8)
     fixed = buf[sec[3][0]:sec[3][0] + sec[3][1]]
     var = buf[sec[4][0]:sec[4][0] + sec[4][1]]
-    rows = []
+    rows, spans = [], []
     for i in range(nrows):
         base = i * row
         vals = []
@@ -125,6 +156,10 @@ def decode(buf: bytes) -> DataTable:
                 vals.append(sdict[struct.unpack_from(">i", fixed, o)[0]])
             elif t == "OBJECT":  # CustomObject: (offset, length) -> int type + bytes
                 vo, ln = struct.unpack_from(">ii", fixed, o)
+                # getCustomObject reads the type int, then slice().limit(length): past the section it throws
+                if vo < 0 or ln < 0 or vo + 4 + ln > len(var):
+                    raise ValueError(f"OBJECT cell ({vo}, {ln}) runs past the {len(var)} variable-size bytes")
+                spans.append((vo, ln))
                 otype = struct.unpack_from(">i", var, vo)[0]
                 vals.append((otype, var[vo + 4:vo + 4 + ln]))
             else:
@@ -139,17 +174,11 @@ def decode(buf: bytes) -> DataTable:
                 continue
             name, vt = key
             md[name] = str(mr.i32()) if vt == "I" else (str(mr.i64()) if vt == "L" else mr.string())
-    return DataTable(names, types, rows, md, exceptions)
+    return DataTable(names, types, rows, md, exceptions, len(var), spans)
 
 
 def _merge(fn, a, b):
-    if fn in (COUNT, SUM):
-        return a + b
-    if fn == MIN:
-        return min(a, b)
-    if fn == MAX:
-        return max(a, b)
-    return np.maximum(a, b)  # HyperLogLog.addAll
+    return merge_intermediate(fn, a, b)
 
 
 def reduce_datatables(q: QueryContext, tables: Sequence[DataTable]) -> ResultTable:
@@ -166,6 +195,8 @@ def reduce_datatables(q: QueryContext, tables: Sequence[DataTable]) -> ResultTab
                     otype, payload = v
                     assert otype == HLL_OBJECT_TYPE
                     v = hll_deserialize(payload)[1]
+                elif a.function == DISTINCTCOUNT:
+                    v = set_deserialize(*v)
                 inter.append(v)
             if key in groups:
                 groups[key] = [_merge(a.function, x, y) for a, x, y in zip(q.aggregations, groups[key], inter)]

@@ -130,6 +130,10 @@ class DistributedQuery:
         statistics describe only the finalisation."""
         import time
 
+        # the library refuses these calls with the same error; raised before torch or a device is touched
+        if any(a.function == "DISTINCTCOUNT" for a in q.aggregations):
+            from .native import PH_ERR_UNSUPPORTED, UnsupportedError
+            raise UnsupportedError(PH_ERR_UNSUPPORTED, "DISTINCTCOUNT on dense partials")
         import torch
         dev = torch.device("cuda", self.ctx.device)
         # run the library on torch's current stream so RCCL and the scan are ordered without host syncs

@@ -18,12 +18,12 @@ from typing import List, Sequence
 import numpy as np
 
 from . import native as N
-from .query import (COUNT, DISTINCTCOUNTHLL, MAX, MIN, SUM, FilterContext, QueryContext, parse_sql)
+from .query import (COUNT, DISTINCTCOUNT, DISTINCTCOUNTHLL, MAX, MIN, SUM, FilterContext, QueryContext, parse_sql)
 from .reduce import ResultTable, reduce_groups
 from .segment import PinnedSegment, SegmentBuffers
 
 _AGG = {COUNT: N.PH_AGG_COUNT, SUM: N.PH_AGG_SUM, MIN: N.PH_AGG_MIN, MAX: N.PH_AGG_MAX,
-        DISTINCTCOUNTHLL: N.PH_AGG_DISTINCTCOUNTHLL}
+        DISTINCTCOUNTHLL: N.PH_AGG_DISTINCTCOUNTHLL, DISTINCTCOUNT: N.PH_AGG_DISTINCTCOUNT}
 _PRED = {"EQ": N.PH_PRED_EQ, "NOT_EQ": N.PH_PRED_NOT_EQ, "IN": N.PH_PRED_IN, "NOT_IN": N.PH_PRED_NOT_IN,
          "RANGE": N.PH_PRED_RANGE}
 
@@ -55,14 +55,36 @@ SCAN_KERNEL_NAMES = {0: "none", 1: "k_scan", 2: "k_agg_lean", 3: "k_agg_sparse",
                      7: "k_scan<MODE_PARTITION> + k_part_agg", 8: "k_part_reg + k_part_agg",
                      9: "k_count_reg",
                      11: "k_group_reg", 12: "k_group_sparse", 14: "k_agg_sparse over roaring containers",
-                     15: "k_group_sparse over roaring containers"}
+                     15: "k_group_sparse over roaring containers",
+                     16: "k_scan, DISTINCTCOUNT bitsets in LDS", 17: "k_scan, DISTINCTCOUNT bitsets in HBM"}
+
+
+@dataclass
+class DistinctColumn:
+    """A DISTINCTCOUNT aggregation's result column: per row a bitset over the aggregation's result dictionary (the
+    reference's dictId bitmap, BaseDistinctAggregateAggregationFunction.java:133-168), the dictionary's values and
+    the rows' popcounts as the device computed them."""
+    bits: np.ndarray    # uint32 [rows, W]: bit i & 31 of word i >> 5 = value i present
+    values: object      # the D dictionary values ascending: numpy array (numeric) or list of str
+    counts: np.ndarray  # int32 [rows]
+
+    def __len__(self):
+        return len(self.counts)
+
+    def value_set(self, row: int) -> frozenset:
+        """The row's value set (convertToValueSet, BaseDistinctAggregateAggregationFunction.java:77-108)."""
+        d = len(self.values)
+        on = np.flatnonzero(np.unpackbits(self.bits[row].view(np.uint8), bitorder="little")[:d])
+        vals = self.values
+        return frozenset(vals[i] for i in on) if isinstance(vals, list) else frozenset(vals[on].tolist())
 
 
 @dataclass
 class IntermediateResult:
     """Combined server-side result: columnar group keys and intermediate aggregation results."""
     key_columns: List[object]   # per group-by column: numpy array (numeric) or list of str
-    agg_columns: List[np.ndarray]  # per aggregation: int64 (COUNT), float64 (SUM/MIN/MAX), uint8[n, m] (HLL)
+    # per aggregation: int64 (COUNT), float64 (SUM/MIN/MAX), uint8[n, m] (HLL), DistinctColumn (DISTINCTCOUNT)
+    agg_columns: List[object]
     num_groups: int
     functions: List[str]
     stats: ExecutionStats
@@ -83,6 +105,8 @@ class IntermediateResult:
                 conv.append(col.tolist())
             elif f == DISTINCTCOUNTHLL:
                 conv.append(list(col))
+            elif f == DISTINCTCOUNT:  # value sets: partial results of different calls merge by value
+                conv.append([col.value_set(i) for i in range(self.num_groups)])
             else:
                 conv.append(col.tolist())
         for i in range(self.num_groups):
@@ -378,6 +402,20 @@ class GpuContext:
         for k, a in enumerate(q.aggregations):
             if a.function == DISTINCTCOUNTHLL:
                 arr = view(L.ph_result_aggregation_data(r, k), n << a.log2m).reshape(n, 1 << a.log2m)
+            elif a.function == DISTINCTCOUNT:
+                dt, es, cnt = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int64()
+                N.check(L.ph_result_distinct_dictionary(r, k, ctypes.byref(dt), ctypes.byref(es), ctypes.byref(cnt)))
+                w, d = L.ph_result_distinct_words(r, k), cnt.value
+                bits = view(L.ph_result_aggregation_data(r, k), 4 * w * n).view(np.uint32).reshape(n, w)
+                raw = view(L.ph_result_distinct_values(r, k), d * es.value)
+                if dt.value == N.PH_STRING:
+                    sv = np.ascontiguousarray(raw).view(f"S{es.value}") if d else np.zeros(0, "S1")
+                    values = np.char.decode(sv, "utf-8").tolist()
+                else:
+                    values = raw.view(_KEY_DTYPE[dt.value])
+                counts = np.zeros(n, np.int32)
+                N.check(L.ph_result_distinct_counts(r, k, counts.ctypes.data))
+                arr = DistinctColumn(bits, values, counts)
             elif a.function == COUNT:
                 arr = view(L.ph_result_aggregation_data(r, k), 8 * n).view(np.int64)
             else:

@@ -24,7 +24,7 @@ DATA_TYPES = {"INT": PH_INT, "LONG": PH_LONG, "FLOAT": PH_FLOAT, "DOUBLE": PH_DO
 
 PH_PRED_EQ, PH_PRED_NOT_EQ, PH_PRED_IN, PH_PRED_NOT_IN, PH_PRED_RANGE = range(5)
 PH_FILTER_AND, PH_FILTER_OR, PH_FILTER_NOT, PH_FILTER_PREDICATE = range(4)
-PH_AGG_COUNT, PH_AGG_SUM, PH_AGG_MIN, PH_AGG_MAX, PH_AGG_DISTINCTCOUNTHLL = range(5)
+PH_AGG_COUNT, PH_AGG_SUM, PH_AGG_MIN, PH_AGG_MAX, PH_AGG_DISTINCTCOUNTHLL, PH_AGG_DISTINCTCOUNT = range(6)
 
 
 class PinotHipError(RuntimeError):
@@ -140,6 +140,8 @@ EXPORTED_SYMBOLS = (
     "ph_raw_forward_index_read", "ph_index_map_lookup", "ph_result_datatable", "ph_selftest_unpack",
     "ph_selftest_unpack_staged", "ph_last_error", "ph_version", "ph_segment_add_star_tree", "ph_segment_num_star_trees",
     "ph_star_tree_check", "ph_star_tree_hll_pair_check",
+    "ph_result_distinct_dictionary", "ph_result_distinct_values", "ph_result_distinct_words",
+    "ph_result_distinct_counts",
 )
 
 _lib = None
@@ -202,6 +204,11 @@ def lib():
         "ph_result_aggregation": ([vp, i32, vp], ctypes.c_int),
         "ph_result_key_data": ([vp, i32], vp),
         "ph_result_aggregation_data": ([vp, i32], vp),
+        "ph_result_distinct_dictionary": ([vp, i32, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i64)],
+                                          ctypes.c_int),
+        "ph_result_distinct_values": ([vp, i32], vp),
+        "ph_result_distinct_words": ([vp, i32], i32),
+        "ph_result_distinct_counts": ([vp, i32, vp], ctypes.c_int),
         "ph_query_dense_layout": ([vp, ctypes.POINTER(Query), ctypes.POINTER(vp), i32, ctypes.POINTER(DenseLayout)],
                                   ctypes.c_int),
         "ph_query_execute_dense": ([vp, ctypes.POINTER(Query), ctypes.POINTER(vp), i32, ctypes.POINTER(vp),

@@ -26,7 +26,8 @@ UNBOUNDED = "*"
 
 # Aggregation function types supported on this path (AggregationFunctionFactory.java:186-263).
 COUNT, SUM, MIN, MAX, DISTINCTCOUNTHLL = "COUNT", "SUM", "MIN", "MAX", "DISTINCTCOUNTHLL"
-SUPPORTED_AGGREGATIONS = (COUNT, SUM, MIN, MAX, DISTINCTCOUNTHLL)
+DISTINCTCOUNT = "DISTINCTCOUNT"  # exact: the size of the value set (DistinctCountAggregationFunction.java:61-68)
+SUPPORTED_AGGREGATIONS = (COUNT, SUM, MIN, MAX, DISTINCTCOUNTHLL, DISTINCTCOUNT)
 DEFAULT_HLL_LOG2M = 8  # CommonConstants.Helix.DEFAULT_HYPERLOGLOG_LOG2M (CommonConstants.java:96-97)
 DEFAULT_NUM_GROUPS_LIMIT = 100_000  # InstancePlanMakerImplV2.DEFAULT_NUM_GROUPS_LIMIT (:72-73)
 DEFAULT_QUERY_LIMIT = 10
@@ -123,7 +124,7 @@ EXPR_OPS = {"*": "times", "-": "minus", "+": "plus"}
 
 @dataclass(frozen=True)
 class AggregationSpec:
-    function: str           # COUNT | SUM | MIN | MAX | DISTINCTCOUNTHLL
+    function: str           # COUNT | SUM | MIN | MAX | DISTINCTCOUNTHLL | DISTINCTCOUNT
     column: Optional[str]   # None for COUNT(*); the first operand of an expression
     log2m: int = DEFAULT_HLL_LOG2M
     column2: Optional[str] = None  # second operand of `column <op> column2`
@@ -277,6 +278,8 @@ class _Parser:
                         raise SqlParseError(f"expressions are supported in SUM/MIN/MAX, not {fn}")
             log2m = DEFAULT_HLL_LOG2M
             if self.accept("op", ","):
+                if fn == DISTINCTCOUNT:
+                    raise SqlParseError("DISTINCTCOUNT takes one argument")
                 log2m = int(self.literal())
             self.expect("op", ")")
             if fn != COUNT and col is None:

@@ -3,7 +3,8 @@
 Mirrors the final steps the reference applies after the server-side combine:
 
 * ``AggregationFunction.extractFinalResult`` -- COUNT -> long, SUM/MIN/MAX -> double,
-  DISTINCTCOUNTHLL -> ``HyperLogLog.cardinality()`` (DistinctCountHLLAggregationFunction.java:362-364).
+  DISTINCTCOUNTHLL -> ``HyperLogLog.cardinality()`` (DistinctCountHLLAggregationFunction.java:362-364),
+  DISTINCTCOUNT -> the value set's size as int (DistinctCountAggregationFunction.java:61-68).
 * ``IndexedTable.finish`` / ``GroupByDataTableReducer.reduceAndSetResults`` -- ORDER BY over group-by
   columns and aggregations (ASC/DESC), then LIMIT (core/data/table/IndexedTable.java:148-173,
   core/query/reduce/GroupByDataTableReducer.java:99).
@@ -20,7 +21,7 @@ from typing import Any, List, Sequence
 
 import numpy as np
 
-from .query import COUNT, DISTINCTCOUNTHLL, MAX, MIN, SUM, QueryContext
+from .query import COUNT, DISTINCTCOUNT, DISTINCTCOUNTHLL, MAX, MIN, SUM, QueryContext
 
 
 def _java_round(x: float) -> int:
@@ -64,6 +65,34 @@ def hll_serialize(registers: np.ndarray, log2m: int) -> bytes:
     return (np.array([log2m, 4 * nwords], dtype=">i4").tobytes() + words.astype(">u4").tobytes())
 
 
+def set_serialize(values, data_type: str) -> bytes:
+    """ObjectSerDeUtils value-set serializers (IntSet / LongSet / FloatSet / DoubleSet / StringSet,
+    ObjectSerDeUtils.java:725-891): int32 BE size, then the values big-endian (strings: int32 BE length + UTF-8).
+    Values are written ascending; the reference writes its fastutil set's iteration order and its deserializers
+    read any order, so this is the same set, not the same bytes."""
+    vals = sorted(values)
+    head = np.array([len(vals)], dtype=">i4").tobytes()
+    if data_type == "STRING":
+        enc = [str(v).encode("utf-8") for v in vals]
+        return head + b"".join(np.array([len(e)], dtype=">i4").tobytes() + e for e in enc)
+    dt = {"INT": ">i4", "LONG": ">i8", "FLOAT": ">f4", "DOUBLE": ">f8"}[data_type]
+    return head + np.asarray(vals, dtype=dt).tobytes()
+
+
+def merge_intermediate(function: str, a, b):
+    """AggregationFunction.merge of two intermediate results of one group: COUNT / SUM add, MIN / MAX, HyperLogLog
+    registers max, DISTINCTCOUNT value sets union (by value: the partial results' dictionaries may differ)."""
+    if function in (COUNT, SUM):
+        return a + b
+    if function == MIN:
+        return min(a, b)
+    if function == MAX:
+        return max(a, b)
+    if function == DISTINCTCOUNT:
+        return frozenset(a) | frozenset(b)
+    return np.maximum(a, b)  # HyperLogLog.addAll
+
+
 @dataclass
 class ResultTable:
     columns: List[str]
@@ -78,12 +107,14 @@ def final_value(spec, value):
         return int(value)
     if spec.function == DISTINCTCOUNTHLL:
         return hll_cardinality(value, spec.log2m)
+    if spec.function == DISTINCTCOUNT:
+        return len(value)
     return float(value)
 
 
 def reduce_groups(q: QueryContext, keys: Sequence[tuple], aggs: Sequence[Sequence[Any]]) -> ResultTable:
     """keys[i]: tuple of group-by values of group i; aggs[i][k]: intermediate result of
-    aggregation k (COUNT int, SUM/MIN/MAX float, HLL register array)."""
+    aggregation k (COUNT int, SUM/MIN/MAX float, HLL register array, DISTINCTCOUNT value set)."""
     finals = [[final_value(q.aggregations[k], a[k]) for k in range(len(q.aggregations))] for a in aggs]
     idx = list(range(len(keys)))
     if q.group_by:
