@@ -152,14 +152,28 @@ typedef struct {
  * CPU plan serves them): multi-device contexts, the dense-partial entry points, segment group trim
  * (min_segment_group_trim_size > 0 with ORDER BY), bitset tables beyond the dense table budget (32 GB, the device table
  * plus the host copy of the rows that can be non-empty) and group key spaces beyond the dense group tables.  A query
- * holding a DISTINCTCOUNT is never answered from a star-tree: it scans the segment's own docs. */
+ * holding a DISTINCTCOUNT is never answered from a star-tree: it scans the segment's own docs.
+ *
+ * PH_AGG_PERCENTILE: the exact percentile (ph_aggregation.percentile, 0..100) of any pinned single-value INT, LONG, FLOAT
+ * or DOUBLE column (a raw column too), the reference's PercentileAggregationFunction: it appends every matched value to a
+ * DoubleArrayList per result holder and sorts at the end (PercentileAggregationFunction.java:77-94, 146-158); here a
+ * result row holds a histogram over the column's result dictionary (the DISTINCTCOUNT bitset with a uint32 counter per
+ * value instead of a bit), which gives the same element with no sort and serves every percentile of the column.  log2m
+ * and column2 are ignored; a non-NONE expr_op and a STRING column are PH_ERR_UNSUPPORTED; a percentile outside 0..100
+ * (or NaN) is PH_ERR_BAD_QUERY (AggregationFunctionFactory.java:376-386).  The shapes DISTINCTCOUNT refuses are refused
+ * with PH_ERR_UNSUPPORTED and their own messages: multi-device contexts, dense partials, segment group trim, histogram
+ * tables beyond the dense table budget (4 bytes per value: the device table plus the host copy of the rows that can be
+ * non-empty), key spaces beyond the dense group tables, more than 4 distinct PERCENTILE columns, and a call whose
+ * segments hold 2^32 docs or more (the counters are uint32; a planner check only).  Never answered from a star-tree or
+ * from metadata: with no filter and no group-by the reference scans too (plan_mode 1). */
 typedef enum {
   PH_AGG_COUNT = 0,
   PH_AGG_SUM = 1,
   PH_AGG_MIN = 2,
   PH_AGG_MAX = 3,
   PH_AGG_DISTINCTCOUNTHLL = 4,
-  PH_AGG_DISTINCTCOUNT = 5
+  PH_AGG_DISTINCTCOUNT = 5,
+  PH_AGG_PERCENTILE = 6
 } ph_aggregation_type;
 
 /* 2-operand expression argument of SUM / MIN / MAX: `column <op> column2`, evaluated per row like the reference's
@@ -174,6 +188,9 @@ typedef struct {
   int32_t log2m;                /* DISTINCTCOUNTHLL; 0 = default 8 (CommonConstants.java:96-97) */
   const char* column2;          /* second operand (expr_op != PH_EXPR_NONE), else NULL */
   int32_t expr_op;              /* ph_expr_op */
+  double percentile;            /* PERCENTILE: 0..100; 0 for every other type */
+  int32_t percentile_name_form; /* PERCENTILE: 0 = `percentile(col, 90.0)`, 1 = `percentile90(col)`: the result column
+                                   name only (PercentileAggregationFunction.java:60-64); 0 for every other type */
 } ph_aggregation;
 
 typedef struct {
@@ -263,8 +280,12 @@ enum {
                                      containers (no doc bitmaps in HBM) */
   PH_KERNEL_SCAN_DISTINCT_LDS = 16, /* k_scan<MODE, ..., LATE = 3>: DISTINCTCOUNT bitsets in the workgroup's LDS, flushed
                                        to the HBM table at the end (plan_mode 1 when they fit, plan_mode 2) */
-  PH_KERNEL_SCAN_DISTINCT_HBM = 17  /* k_scan<MODE, ..., LATE = 3>: DISTINCTCOUNT bits ORed straight into the HBM table
+  PH_KERNEL_SCAN_DISTINCT_HBM = 17, /* k_scan<MODE, ..., LATE = 3>: DISTINCTCOUNT bits ORed straight into the HBM table
                                        (plan_mode 1 otherwise, plan_mode 3) */
+  PH_KERNEL_SCAN_HIST_LDS = 18,     /* k_scan<MODE, ..., LATE = 4>: PERCENTILE histograms (and any DISTINCTCOUNT bitsets
+                                       of the query) in the workgroup's LDS, flushed at the end (plan_mode 1 or 2) */
+  PH_KERNEL_SCAN_HIST_HBM = 19      /* k_scan<MODE, ..., LATE = 4>: PERCENTILE counters added straight into the HBM
+                                       table, equal (row, id) lanes of a wave combined first (plan_mode 1 or 3) */
 };
 
 /* ------------------------------------------------------------------ context */
@@ -415,7 +436,9 @@ const void* ph_result_key_data(const ph_result* r, int32_t group_by_index);
 /* intermediate result of aggregation i for every row: COUNT int64, SUM/MIN/MAX double,
  * DISTINCTCOUNTHLL uint8[2^log2m] raw registers (HyperLogLog.addAll = register-wise max),
  * DISTINCTCOUNT uint32[W] bitset over the aggregation's result dictionary, W = ceil(D / 32): bit i & 31 of word
- * i >> 5 set means value i of the dictionary is present; bits past D are zero */
+ * i >> 5 set means value i of the dictionary is present; bits past D are zero,
+ * PERCENTILE uint32[D] histogram over the aggregation's result dictionary: the matched docs of each value
+ * (PERCENTILE aggregations over one column return the same histogram) */
 int ph_result_aggregation(const ph_result* r, int32_t aggregation_index, void* out);
 const void* ph_result_aggregation_data(const ph_result* r, int32_t aggregation_index);
 /* DISTINCTCOUNT aggregation k.  Its result dictionary is the table dictionary of the column (ph_table_set_dictionary)
@@ -435,6 +458,21 @@ int ph_result_distinct_dictionary(const ph_result* r, int32_t aggregation_index,
 const void* ph_result_distinct_values(const ph_result* r, int32_t aggregation_index);
 int32_t ph_result_distinct_words(const ph_result* r, int32_t aggregation_index);
 int ph_result_distinct_counts(const ph_result* r, int32_t aggregation_index, int32_t* out);
+/* PERCENTILE aggregation k.  Its result dictionary is chosen as a DISTINCTCOUNT's is; results of different calls may
+ * have different dictionaries: merge them by value.
+ *   ph_result_percentile_dictionary  stored ph_data_type, bytes per value and the number of values D
+ *   ph_result_percentile_values      the D values ascending, laid out as ph_result_key_data lays out group keys
+ *                                    (valid until ph_result_destroy)
+ *   ph_result_percentile_final       one double per result row, exactly the reference's final result
+ *                                    (PercentileAggregationFunction.java:146-158) with n = the row's histogram total:
+ *                                    n = 0 gives -inf; p = 100 the largest present value; otherwise the value of rank
+ *                                    (int)((double)n * p / 100.0), clamped to n - 1, in ascending order.  The rank is
+ *                                    found on the device in dictId space (k_percentile_finish); the value is converted
+ *                                    to double last (a LONG beyond 2^53 rounds as getDoubleValuesSV rounds it). */
+int ph_result_percentile_dictionary(const ph_result* r, int32_t aggregation_index, int32_t* data_type,
+                                    int32_t* entry_size, int64_t* count);
+const void* ph_result_percentile_values(const ph_result* r, int32_t aggregation_index);
+int ph_result_percentile_final(const ph_result* r, int32_t aggregation_index, double* out);
 
 /* ------------------------------------------------------------------ server -> broker DataTable */
 /* The result as the DataTable V4 bytes the reference's server returns for it (InstanceResponseBlock.toDataTable:
@@ -447,7 +485,12 @@ int ph_result_distinct_counts(const ph_result* r, int32_t aggregation_index, int
  * does -- IntSet(9), LongSet(15), FloatSet(16), DoubleSet(17), StringSet(18) (ObjectSerDeUtils.java:113-123, serialisers
  * :725-891): int32 BE size, then the values (strings: int32 BE length + UTF-8).  Values are written ascending; the
  * reference writes its fastutil set's iteration order and its deserialisers do not depend on the order, so the bytes
- * are an equal set, not byte-identical (parity unpinned). */
+ * are an equal set, not byte-identical (parity unpinned).
+ * A PERCENTILE column is OBJECT type 3, DoubleArrayList (ObjectSerDeUtils.java:328-357): int32 BE size, then the doubles
+ * BE -- each value of the row's histogram written `count` times, ascending, 8 bytes per matched doc as the reference's.
+ * The reference writes arrival order and sorts at the broker: equal multisets, not byte-identical (parity unpinned).
+ * Its column name is getResultColumnName's (PercentileAggregationFunction.java:60-64): `percentile90(col)` for name
+ * form 1, `percentile(col, 90.0)` for name form 0 (the percentile as Java's Double.toString writes plain decimals). */
 typedef struct {
   const char* key;
   const char* value;

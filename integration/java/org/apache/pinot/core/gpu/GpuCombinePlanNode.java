@@ -107,8 +107,8 @@ public class GpuCombinePlanNode extends CombinePlanNode {
     }
 
     private ByteBuffer aggColumn(long res, int k, AggregationFunction f) {
-      // (a DISTINCTCOUNT column is read through GpuResultSchema.DistinctColumn; its rows are 4 * W bytes, W >= 1)
-      int bytes = f.getType() == AggregationFunctionType.DISTINCTCOUNT ? 4
+      // (a DISTINCTCOUNT / PERCENTILE column is read through GpuResultSchema.rowObjects; its rows are 4 * W bytes, W >= 1)
+      int bytes = f.getType() == AggregationFunctionType.DISTINCTCOUNT || f.getType() == AggregationFunctionType.PERCENTILE ? 4
           : f.getType() == AggregationFunctionType.DISTINCTCOUNTHLL
           ? 1 << ((DistinctCountHLLAggregationFunction) f).getLog2m() : 8;
       return PinotHipJni.resultAggregationBuffer(res, k, bytes).order(ByteOrder.nativeOrder());
@@ -118,8 +118,8 @@ public class GpuCombinePlanNode extends CombinePlanNode {
       AggregationFunction[] functions = _queryContext.getAggregationFunctions();
       List<Object> results = new ArrayList<>(functions.length);
       for (int k = 0; k < functions.length; k++) {
-        results.add(functions[k].getType() == AggregationFunctionType.DISTINCTCOUNT
-            ? new GpuResultSchema.DistinctColumn(res, k).set(0) : intermediate(functions[k], aggColumn(res, k, functions[k]), 0));
+        GpuResultSchema.RowObjects objects = GpuResultSchema.rowObjects(res, k, functions[k]);  // DISTINCTCOUNT / PERCENTILE
+        results.add(objects != null ? objects.row(0) : intermediate(functions[k], aggColumn(res, k, functions[k]), 0));
       }
       return new AggregationResultsBlock(functions, results, _queryContext);
     }
@@ -144,14 +144,12 @@ public class GpuCombinePlanNode extends CombinePlanNode {
             : ColumnDataType.STRING;
       }
       ByteBuffer[] aggs = new ByteBuffer[functions.length];
-      GpuResultSchema.DistinctColumn[] distinct = new GpuResultSchema.DistinctColumn[functions.length];
+      GpuResultSchema.RowObjects[] distinct = new GpuResultSchema.RowObjects[functions.length];
       for (int k = 0; k < functions.length; k++) {
         names[nk + k] = functions[k].getResultColumnName();
         types[nk + k] = functions[k].getIntermediateResultColumnType();
         aggs[k] = aggColumn(res, k, functions[k]);
-        if (functions[k].getType() == AggregationFunctionType.DISTINCTCOUNT) {
-          distinct[k] = new GpuResultSchema.DistinctColumn(res, k);  // once per aggregation, not per row
-        }
+        distinct[k] = GpuResultSchema.rowObjects(res, k, functions[k]);  // once per aggregation, not per row (else null)
       }
       DataSchema schema = new DataSchema(names, types);
       // the server-level table of GroupByCombineOperator (resultSize / trim as IndexedTable.java:63-91)
@@ -185,7 +183,7 @@ public class GpuCombinePlanNode extends CombinePlanNode {
           row[g] = v;
         }
         for (int k = 0; k < functions.length; k++) {
-          row[nk + k] = distinct[k] != null ? distinct[k].set(r) : intermediate(functions[k], aggs[k], r);
+          row[nk + k] = distinct[k] != null ? distinct[k].row(r) : intermediate(functions[k], aggs[k], r);
         }
         table.upsert(new Key(kv), new Record(row));
       }

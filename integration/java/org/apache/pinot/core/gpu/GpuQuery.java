@@ -25,7 +25,7 @@ import org.apache.pinot.segment.spi.AggregationFunctionType;
  * QueryContext -> the ph_query descriptor of PinotHipJni.queryExecute (the Java twin of pinot_amd/query.py +
  * engine._QueryStruct).  Returns null for shapes outside the GPU path, so the plan maker keeps the CPU plan:
  * filtered aggregations, star-tree, null handling, non-identifier group-by expressions, aggregations other than
- * COUNT / SUM / MIN / MAX / DISTINCTCOUNTHLL / DISTINCTCOUNT (over a column; SUM / MIN / MAX also over a 2-operand
+ * COUNT / SUM / MIN / MAX / DISTINCTCOUNTHLL / DISTINCTCOUNT / PERCENTILE (over a column; SUM / MIN / MAX also over a 2-operand
  * mult/sub/add), predicates other than
  * EQ / NOT_EQ / IN / NOT_IN / RANGE on identifiers, and a segment group trim (GroupByOperator.java:114-130) ordered
  * by anything but group-by columns and aggregations.
@@ -261,12 +261,13 @@ public final class GpuQuery {
       return _preds.size() - 1;
     }
 
-    // AggregationFunction -> {type, column, log2m, column2, exprOp} or null (not on the GPU path)
+    // AggregationFunction -> {type, column, log2m, column2, exprOp, percentile bits high, low, percentileNameForm} or null
+    // (not on the GPU path).  The last three are zero unless the function is a PERCENTILE.
     int[] aggregation(AggregationFunction f) {
       AggregationFunctionType t = f.getType();
       List<ExpressionContext> in = f.getInputExpressions();
       if (t == AggregationFunctionType.COUNT) {
-        return new int[]{PinotHipJni.AGG_COUNT, -1, 0, -1, PinotHipJni.EXPR_NONE};
+        return new int[]{PinotHipJni.AGG_COUNT, -1, 0, -1, PinotHipJni.EXPR_NONE, 0, 0, 0};
       }
       int type;
       switch (t) {
@@ -285,13 +286,30 @@ public final class GpuQuery {
         case DISTINCTCOUNT:  // exact: a bitset over the column's result dictionary (ph_result_distinct_*)
           type = PinotHipJni.AGG_DISTINCTCOUNT;
           break;
+        case PERCENTILE:  // exact: a histogram over the column's result dictionary (ph_result_percentile_*)
+          type = PinotHipJni.AGG_PERCENTILE;
+          break;
         default:
           return null;
       }
       ExpressionContext e = in.get(0);
+      if (type == PinotHipJni.AGG_PERCENTILE) {
+        if (e.getType() != ExpressionContext.Type.IDENTIFIER) {
+          return null;
+        }
+        // the function keeps its percentile and spelling private; its result column name carries both
+        // (PercentileAggregationFunction.java:60-64): percentile90(col) | percentile(col, 90.0)
+        String name = f.getResultColumnName();
+        int open = name.indexOf('(');
+        int form = open > "percentile".length() ? 1 : 0;
+        double p = form == 1 ? Integer.parseInt(name.substring("percentile".length(), open))
+            : Double.parseDouble(name.substring(name.lastIndexOf(", ") + 2, name.length() - 1));
+        long bits = Double.doubleToRawLongBits(p);
+        return new int[]{type, str(e.getIdentifier()), 0, -1, PinotHipJni.EXPR_NONE, (int) (bits >>> 32), (int) bits, form};
+      }
       int log2m = t == AggregationFunctionType.DISTINCTCOUNTHLL ? ((DistinctCountHLLAggregationFunction) f).getLog2m() : 0;
       if (e.getType() == ExpressionContext.Type.IDENTIFIER) {
-        return new int[]{type, str(e.getIdentifier()), log2m, -1, PinotHipJni.EXPR_NONE};
+        return new int[]{type, str(e.getIdentifier()), log2m, -1, PinotHipJni.EXPR_NONE, 0, 0, 0};
       }
       // SUM(a*b) / SUM(a-b) / SUM(a+b): one 2-operand transform over identifiers (ProjectPlanNode.java:82)
       if (e.getType() == ExpressionContext.Type.FUNCTION && type != PinotHipJni.AGG_DISTINCTCOUNTHLL
@@ -303,7 +321,7 @@ public final class GpuQuery {
         List<ExpressionContext> args = fn.getArguments();
         if (op > 0 && args.size() == 2 && args.get(0).getType() == ExpressionContext.Type.IDENTIFIER
             && args.get(1).getType() == ExpressionContext.Type.IDENTIFIER) {
-          return new int[]{type, str(args.get(0).getIdentifier()), 0, str(args.get(1).getIdentifier()), op};
+          return new int[]{type, str(args.get(0).getIdentifier()), 0, str(args.get(1).getIdentifier()), op, 0, 0, 0};
         }
       }
       return null;

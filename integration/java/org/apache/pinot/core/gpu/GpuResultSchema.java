@@ -1,5 +1,6 @@
 package org.apache.pinot.core.gpu;
 
+import it.unimi.dsi.fastutil.doubles.DoubleArrayList;
 import it.unimi.dsi.fastutil.doubles.DoubleOpenHashSet;
 import it.unimi.dsi.fastutil.floats.FloatOpenHashSet;
 import it.unimi.dsi.fastutil.ints.IntOpenHashSet;
@@ -14,6 +15,7 @@ import org.apache.pinot.common.utils.DataSchema;
 import org.apache.pinot.common.utils.DataSchema.ColumnDataType;
 import org.apache.pinot.core.query.aggregation.function.AggregationFunction;
 import org.apache.pinot.core.query.request.context.QueryContext;
+import org.apache.pinot.segment.spi.AggregationFunctionType;
 
 
 /**
@@ -21,7 +23,9 @@ import org.apache.pinot.core.query.request.context.QueryContext;
  * expressions with the stored types of their key columns, then each function's result column name and intermediate
  * type.  Also the intermediate result of DISTINCTCOUNT: the value set the reference's convertToValueSet builds from its
  * dictId bitmap (BaseDistinctAggregateAggregationFunction.java:77-108), here from the result dictionary's values x the
- * row's bitset.  (Written against the reference API; not compiled in this repository's build.)
+ * row's bitset; and of PERCENTILE: the DoubleArrayList of matched values (PercentileAggregationFunction.java:77-94),
+ * here each value of the result dictionary repeated by the row's histogram count, ascending (the reference sorts the list
+ * before it reads an element, :146-158).  (Written against the reference API; not compiled in this repository's build.)
  */
 final class GpuResultSchema {
   private GpuResultSchema() {
@@ -37,9 +41,68 @@ final class GpuResultSchema {
     }
   }
 
+  /** An aggregation whose intermediate result is an object built from a per-row table over a result dictionary. */
+  interface RowObjects {
+    Object row(int row);
+  }
+
+  /** The object column of aggregation {@code k}, or null when its intermediate result is a plain value. */
+  static RowObjects rowObjects(long res, int k, AggregationFunction f) {
+    if (f.getType() == AggregationFunctionType.DISTINCTCOUNT) {
+      return new DistinctColumn(res, k);
+    }
+    if (f.getType() == AggregationFunctionType.PERCENTILE) {
+      return new HistogramColumn(res, k);
+    }
+    return null;
+  }
+
+  /** PERCENTILE aggregation {@code k} of a result (ph_result_percentile_*): uint32[D] histogram rows over the D values
+   *  of its result dictionary. */
+  static final class HistogramColumn implements RowObjects {
+    private final int _type;
+    private final int _entrySize;
+    private final long _count;
+    private final ByteBuffer _hist;
+    private final ByteBuffer _values;
+
+    HistogramColumn(long res, int k) {
+      int[] te = new int[2];
+      _count = PinotHipJni.resultPercentileDictionary(res, k, te);
+      _type = te[0];
+      _entrySize = te[1];
+      _hist = PinotHipJni.resultAggregationBuffer(res, k, 4 * (int) Math.max(1, _count)).order(ByteOrder.nativeOrder());
+      _values = PinotHipJni.resultPercentileValues(res, k).order(ByteOrder.nativeOrder());
+    }
+
+    /** Row {@code row}: the matched values as doubles (getDoubleValuesSV's conversion), ascending. */
+    @Override
+    public Object row(int row) {
+      DoubleArrayList list = new DoubleArrayList();
+      long stride = Math.max(1, _count);
+      for (int i = 0; i < _count; i++) {
+        long n = _hist.getInt((int) (4 * (row * stride + i))) & 0xffffffffL;
+        if (n == 0) {
+          continue;
+        }
+        double v;
+        switch (_type) {
+          case PinotHipJni.INT: v = _values.getInt(_entrySize * i); break;
+          case PinotHipJni.LONG: v = (double) _values.getLong(_entrySize * i); break;
+          case PinotHipJni.FLOAT: v = _values.getFloat(_entrySize * i); break;
+          default: v = _values.getDouble(_entrySize * i);
+        }
+        for (long j = 0; j < n; j++) {
+          list.add(v);
+        }
+      }
+      return list;
+    }
+  }
+
   /** DISTINCTCOUNT aggregation {@code k} of a result: its dictionary and buffers are fetched once (three JNI calls, two
    *  direct buffers over the whole column), then {@link #set} builds any row's value set from them. */
-  static final class DistinctColumn {
+  static final class DistinctColumn implements RowObjects {
     private final int _type;
     private final int _entrySize;
     private final int _words;
@@ -55,6 +118,11 @@ final class GpuResultSchema {
       _words = tew[2];
       _bits = PinotHipJni.resultAggregationBuffer(res, k, 4 * _words).order(ByteOrder.nativeOrder());
       _values = PinotHipJni.resultDistinctValues(res, k).order(ByteOrder.nativeOrder());
+    }
+
+    @Override
+    public Object row(int row) {
+      return set(row);
     }
 
     /** Row {@code row}: IntOpenHashSet / LongOpenHashSet / FloatOpenHashSet / DoubleOpenHashSet /

@@ -178,8 +178,8 @@ public class GpuSegmentPlanNode implements PlanNode {
       AggregationFunction[] functions = _queryContext.getAggregationFunctions();
       List<Object> results = new java.util.ArrayList<>(functions.length);
       for (int k = 0; k < functions.length; k++) {
-        results.add(functions[k].getType() == AggregationFunctionType.DISTINCTCOUNT
-            ? new GpuResultSchema.DistinctColumn(res, k).set(0) : intermediate(functions[k], column(res, k, functions[k]), 0));
+        GpuResultSchema.RowObjects objects = GpuResultSchema.rowObjects(res, k, functions[k]);  // DISTINCTCOUNT / PERCENTILE
+        results.add(objects != null ? objects.row(0) : intermediate(functions[k], column(res, k, functions[k]), 0));
       }
       return new AggregationResultsBlock(functions, results, _queryContext);
     }
@@ -205,11 +205,11 @@ public class GpuSegmentPlanNode implements PlanNode {
       GroupByResultHolder[] holders = new GroupByResultHolder[functions.length];
       for (int k = 0; k < functions.length; k++) {
         ByteBuffer col = column(res, k, functions[k]);
-        if (functions[k].getType() == AggregationFunctionType.DISTINCTCOUNT) {
+        GpuResultSchema.RowObjects dc = GpuResultSchema.rowObjects(res, k, functions[k]);  // DISTINCTCOUNT / PERCENTILE
+        if (dc != null) {
           ObjectGroupByResultHolder h = new ObjectGroupByResultHolder(n, n);
-          GpuResultSchema.DistinctColumn dc = new GpuResultSchema.DistinctColumn(res, k);
           for (int r = 0; r < n; r++) {
-            h.setValueForKey(r, dc.set(r));
+            h.setValueForKey(r, dc.row(r));
           }
           holders[k] = h;
         } else if (functions[k].getType() == AggregationFunctionType.DISTINCTCOUNTHLL) {
@@ -275,8 +275,8 @@ public class GpuSegmentPlanNode implements PlanNode {
   }
 
   static ByteBuffer column(long res, int k, AggregationFunction f) {
-    // (a DISTINCTCOUNT column is read through GpuResultSchema.DistinctColumn; its rows are 4 * W bytes, W >= 1)
-    int bytes = f.getType() == AggregationFunctionType.DISTINCTCOUNT ? 4
+    // (a DISTINCTCOUNT / PERCENTILE column is read through GpuResultSchema.rowObjects; its rows are 4 * W bytes, W >= 1)
+    int bytes = f.getType() == AggregationFunctionType.DISTINCTCOUNT || f.getType() == AggregationFunctionType.PERCENTILE ? 4
         : f.getType() == AggregationFunctionType.DISTINCTCOUNTHLL
         ? 1 << ((DistinctCountHLLAggregationFunction) f).getLog2m() : 8;
     return PinotHipJni.resultAggregationBuffer(res, k, bytes).order(ByteOrder.nativeOrder());

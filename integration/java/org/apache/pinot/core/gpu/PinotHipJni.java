@@ -18,7 +18,7 @@ public final class PinotHipJni {
   // ph_data_type / ph_aggregation_type / ph_filter_type / ph_predicate_type / ph_expr_op
   public static final int INT = 0, LONG = 1, FLOAT = 2, DOUBLE = 3, STRING = 4;
   public static final int AGG_COUNT = 0, AGG_SUM = 1, AGG_MIN = 2, AGG_MAX = 3, AGG_DISTINCTCOUNTHLL = 4,
-      AGG_DISTINCTCOUNT = 5;
+      AGG_DISTINCTCOUNT = 5, AGG_PERCENTILE = 6;
   public static final int FILTER_AND = 0, FILTER_OR = 1, FILTER_NOT = 2, FILTER_PREDICATE = 3;
   public static final int PRED_EQ = 0, PRED_NOT_EQ = 1, PRED_IN = 2, PRED_NOT_IN = 3, PRED_RANGE = 4;
   public static final int EXPR_NONE = 0, EXPR_MULT = 1, EXPR_SUB = 2, EXPR_ADD = 3;
@@ -57,6 +57,10 @@ public final class PinotHipJni {
   // the D dictionary values laid out like group keys, and the rows' bitsets through resultAggregationBuffer(.., 4 * W)
   static native long resultDistinctDictionary(long result, int aggIndex, int[] typeEntrySizeWords);
   static native ByteBuffer resultDistinctValues(long result, int aggIndex);
+  // PERCENTILE aggregation k (ph_result_percentile_*): {data type, entry size} + the value count D, the D dictionary
+  // values laid out like group keys, and the rows' uint32[D] histograms through resultAggregationBuffer(.., 4 * D)
+  static native long resultPercentileDictionary(long result, int aggIndex, int[] typeEntrySize);
+  static native ByteBuffer resultPercentileValues(long result, int aggIndex);
   static native void resultStats(long result, long[] out7);                              // ph_result_stats
   static native void resultDestroy(long result);                                         // ph_result_destroy
 }

@@ -141,7 +141,8 @@ JNIEXPORT void JNICALL FN(tableSetColumnType)(JNIEnv* env, jclass c, jlong ctx, 
  *    per filter node: type, numChildren, predicate, child...,
  *    per predicate: type, column, numValues, value..., lower, upper, lowerInclusive, upperInclusive,
  *    per group-by column: column,
- *    per aggregation: type, column, log2m, column2, exprOp,
+ *    per aggregation: type, column, log2m, column2, exprOp, percentile bits high, percentile bits low,
+ *                     percentileNameForm (the last three zero unless type is PH_AGG_PERCENTILE),
  *    optional: numOrderBy, (kind, index, asc) x numOrderBy, limit, minSegmentGroupTrimSize]
  * decoded into `q`; the arrays it points into are owned by `b` (query_bufs_free).  Returns 0, or -1 for a malformed
  * descriptor (every read is bounds-checked). */
@@ -224,6 +225,14 @@ static int decode_query(const jint* desc, jsize nd, const char** strs, jsize ns,
     NEXT(tmp);
     b->aggs[i].column2 = S(tmp);
     NEXT(b->aggs[i].expr_op);
+    { /* ph_aggregation.percentile as the two halves of its IEEE-754 bits (Double.doubleToRawLongBits) */
+      jint hi = 0, lo = 0;
+      NEXT(hi);
+      NEXT(lo);
+      const uint64_t bits = ((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo;
+      memcpy(&b->aggs[i].percentile, &bits, sizeof bits);
+    }
+    NEXT(b->aggs[i].percentile_name_form);
   }
   if (k < nd) { /* optional trailing block: ORDER BY + LIMIT + minSegmentGroupTrimSize [+ skipStarTree] */
     NEXT(q->num_order_by);
@@ -367,6 +376,24 @@ JNIEXPORT jobject JNICALL FN(resultDistinctValues)(JNIEnv* env, jclass c, jlong 
   int64_t count = 0;
   if (throw_ph(env, ph_result_distinct_dictionary(PTR(res), a, &type, &es, &count))) return NULL;
   return (*env)->NewDirectByteBuffer(env, (void*)ph_result_distinct_values(PTR(res), a), (jlong)count * es);
+}
+
+/* ph_result_percentile_dictionary: out = {data type, entry size}; returns the value count D.  (Uncompiled here: no
+ * JDK in this repository's build.) */
+JNIEXPORT jlong JNICALL FN(resultPercentileDictionary)(JNIEnv* env, jclass c, jlong res, jint a, jintArray out) {
+  int32_t type = 0, es = 0;
+  int64_t count = 0;
+  if (throw_ph(env, ph_result_percentile_dictionary(PTR(res), a, &type, &es, &count))) return 0;
+  const jint v[2] = {type, es};
+  (*env)->SetIntArrayRegion(env, out, 0, 2, v);
+  return (jlong)count;
+}
+
+JNIEXPORT jobject JNICALL FN(resultPercentileValues)(JNIEnv* env, jclass c, jlong res, jint a) {
+  int32_t type = 0, es = 0;
+  int64_t count = 0;
+  if (throw_ph(env, ph_result_percentile_dictionary(PTR(res), a, &type, &es, &count))) return NULL;
+  return (*env)->NewDirectByteBuffer(env, (void*)ph_result_percentile_values(PTR(res), a), (jlong)count * es);
 }
 
 /* ph_exec_stats: numDocsScanned, numEntriesScannedInFilter, numEntriesScannedPostFilter, numTotalDocs,

@@ -321,10 +321,18 @@ int ph_table_set_column_type(ph_ctx* ctx, const char* column, int32_t data_type)
   });
 }
 
-static bool has_distinct_count(const ph_query* q) {
+static bool has_aggregation(const ph_query* q, int32_t type) {
   for (int32_t k = 0; q && q->aggregations && k < q->num_aggregations; ++k)
-    if (q->aggregations[k].type == PH_AGG_DISTINCTCOUNT) return true;
+    if (q->aggregations[k].type == type) return true;
   return false;
+}
+
+// DISTINCTCOUNT bitsets and PERCENTILE histograms are neither merged across devices, nor trimmed per segment, nor
+// kept as dense partials: the name of the first such function of the query, or nullptr
+static const char* row_table_function(const ph_query* q) {
+  if (has_aggregation(q, PH_AGG_DISTINCTCOUNT)) return "DISTINCTCOUNT";
+  if (has_aggregation(q, PH_AGG_PERCENTILE)) return "PERCENTILE";
+  return nullptr;
 }
 
 int ph_query_execute(ph_ctx* ctx, const ph_query* query, ph_segment* const* segments, int32_t num_segments,
@@ -332,11 +340,12 @@ int ph_query_execute(ph_ctx* ctx, const ph_query* query, ph_segment* const* segm
   return guarded([&] {
     if (!ctx || !out) fail(PH_ERR_INVALID_ARGUMENT, "null argument");
     *out = nullptr;
-    // DISTINCTCOUNT bitsets are neither merged across devices nor trimmed per segment: the CPU plan serves those
-    if (has_distinct_count(query) && ctx->devs.size() > 1)
-      fail(PH_ERR_UNSUPPORTED, "DISTINCTCOUNT on a multi-device context");
-    if (has_distinct_count(query) && query->min_segment_group_trim_size > 0 && query->num_group_by > 0 && query->num_order_by > 0)
-      fail(PH_ERR_UNSUPPORTED, "DISTINCTCOUNT with segment group trim (minSegmentGroupTrimSize)");
+    // the CPU plan serves those
+    if (const char* fn = row_table_function(query)) {
+      if (ctx->devs.size() > 1) fail(PH_ERR_UNSUPPORTED, std::string(fn) + " on a multi-device context");
+      if (query->min_segment_group_trim_size > 0 && query->num_group_by > 0 && query->num_order_by > 0)
+        fail(PH_ERR_UNSUPPORTED, std::string(fn) + " with segment group trim (minSegmentGroupTrimSize)");
+    }
     if (ctx->devs.size() > 1)
       *out = multi_execute(ctx, query, segments, num_segments);  // per device, merged in the library
     else if (query && query->min_segment_group_trim_size > 0 && query->num_group_by > 0 && query->num_order_by > 0)
@@ -421,7 +430,7 @@ static Context* dense_device(ph_ctx* ctx, ph_segment* const* segs, int32_t n) {
 }
 
 static void reject_dense_shapes(const ph_query* q) {
-  if (has_distinct_count(q)) fail(PH_ERR_UNSUPPORTED, "DISTINCTCOUNT on dense partials");
+  if (const char* fn = row_table_function(q)) fail(PH_ERR_UNSUPPORTED, std::string(fn) + " on dense partials");
   if (q && q->min_segment_group_trim_size > 0 && q->num_group_by > 0 && q->num_order_by > 0)
     fail(PH_ERR_UNSUPPORTED, "segment group trim (minSegmentGroupTrimSize) on dense partials");
 }
@@ -538,6 +547,36 @@ int ph_result_distinct_counts(const ph_result* r, int32_t k, int32_t* out) {
     const ph_result::Distinct& d = distinct_of(r, k);
     if (!out) fail(PH_ERR_INVALID_ARGUMENT, "null output");
     memcpy(out, d.counts.data(), sizeof(int32_t) * d.counts.size());
+  });
+}
+
+// ---- PERCENTILE result columns
+static const ph_result::Percentile& percentile_of(const ph_result* r, int32_t k) {
+  if (!r || k < 0 || k >= (int32_t)r->percentile.size() || !r->percentile[k].set)
+    fail(PH_ERR_INVALID_ARGUMENT, "not a PERCENTILE aggregation");
+  return r->percentile[k];
+}
+
+int ph_result_percentile_dictionary(const ph_result* r, int32_t k, int32_t* data_type, int32_t* entry_size,
+                                    int64_t* count) {
+  return guarded([&] {
+    const ph_result::Percentile& d = percentile_of(r, k);
+    if (data_type) *data_type = d.data_type;
+    if (entry_size) *entry_size = d.entry_size;
+    if (count) *count = d.count;
+  });
+}
+
+const void* ph_result_percentile_values(const ph_result* r, int32_t k) {
+  if (!r || k < 0 || k >= (int32_t)r->percentile.size() || !r->percentile[k].set) return nullptr;
+  return r->percentile[k].values.data();
+}
+
+int ph_result_percentile_final(const ph_result* r, int32_t k, double* out) {
+  return guarded([&] {
+    const ph_result::Percentile& d = percentile_of(r, k);
+    if (!out) fail(PH_ERR_INVALID_ARGUMENT, "null output");
+    memcpy(out, d.finals.data(), sizeof(double) * d.finals.size());
   });
 }
 

@@ -10,7 +10,7 @@
 //   Data schema (DataSchema.toBytes): numColumns, UTF-8 names, UTF-8 ColumnDataType names.  Columns: the group-by
 //   identifiers (GroupByOperator.java:76-81; stored types INT / LONG / FLOAT / DOUBLE / STRING) then one column per
 //   aggregation named AggregationFunction.getResultColumnName() (`count(*)`, `sum(m)`, `sum(times(a,b))`) with its
-//   intermediate type (COUNT LONG, SUM / MIN / MAX DOUBLE, DISTINCTCOUNTHLL / DISTINCTCOUNT OBJECT).
+//   intermediate type (COUNT LONG, SUM / MIN / MAX DOUBLE, DISTINCTCOUNTHLL / DISTINCTCOUNT / PERCENTILE OBJECT).
 //   Fixed-size rows (DataTableUtils.computeColumnOffsets): INT / FLOAT / STRING (a string-dictionary id, assigned in
 //   first-seen order, DataTableBuilderV4.setColumn(String)) 4 bytes, LONG / DOUBLE 8, OBJECT 8 = (offset into the
 //   variable section, byte length); the variable section holds int objectType (ObjectSerDeUtils.ObjectType
@@ -21,6 +21,9 @@
 //   table size, insertion order within a bucket) -- so the bytes equal the reference's for the same map.
 // Row order is the result's (keys ascending); the reference's server emits its IndexedTable's iteration order,
 // which carries no meaning for the broker (GroupByDataTableReducer merges by key).
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <unordered_map>
@@ -101,10 +104,37 @@ std::vector<std::pair<std::string, std::string>> hashmap_order(const std::vector
   return out;
 }
 
+// Java's Double.toString of a percentile (0..100): the shortest digits that read back as the same double, at least
+// one digit after the point, computerised scientific notation below 1e-3 ("1.0E-4")
+std::string java_double_string(double v) {
+  char buf[40];
+  if (v != 0.0 && std::fabs(v) < 1e-3) {
+    for (int prec = 0; prec <= 16; ++prec) {
+      snprintf(buf, sizeof buf, "%.*e", prec, v);
+      if (strtod(buf, nullptr) == v) break;
+    }
+    std::string t(buf);
+    const size_t e = t.find('e');
+    std::string mant = t.substr(0, e);
+    if (mant.find('.') == std::string::npos) mant += ".0";
+    return mant + "E" + std::to_string(atoi(t.c_str() + e + 1));
+  }
+  for (int prec = 1; prec <= 17; ++prec) {  // plain decimals: 90.0, 99.9, 12.5, 0.001
+    snprintf(buf, sizeof buf, "%.*f", prec, v);
+    if (strtod(buf, nullptr) == v) break;
+  }
+  return buf;
+}
+
 std::string agg_column_name(const ph_aggregation& a) {
-  static const char* fn[] = {"count", "sum", "min", "max", "distinctcounthll", "distinctcount"};
+  static const char* fn[] = {"count", "sum", "min", "max", "distinctcounthll", "distinctcount", "percentile"};
+  if (a.type < 0 || a.type > PH_AGG_PERCENTILE) fail(PH_ERR_INVALID_ARGUMENT, "unknown aggregation");
   if (a.type == PH_AGG_COUNT) return "count(*)";
-  if (a.type < 0 || a.type > PH_AGG_DISTINCTCOUNT) fail(PH_ERR_INVALID_ARGUMENT, "unknown aggregation");
+  if (a.type == PH_AGG_PERCENTILE) {  // PercentileAggregationFunction.getResultColumnName (:60-64)
+    const std::string col = a.column ? a.column : "";
+    if (a.percentile_name_form) return std::string(fn[a.type]) + std::to_string((int)a.percentile) + "(" + col + ")";
+    return std::string(fn[a.type]) + "(" + col + ", " + java_double_string(a.percentile) + ")";
+  }
   std::string arg = a.column ? a.column : "";
   if (a.expr_op != PH_EXPR_NONE) {  // FunctionContext.toString of the compiled arithmetic (TransformFunctionType)
     static const char* op[] = {"", "times", "minus", "plus"};
@@ -146,7 +176,7 @@ std::vector<uint8_t> result_to_datatable(const ph_result* r, const ph_query* q, 
   for (int k = 0; k < na; ++k) {
     names.push_back(agg_column_name(q->aggregations[k]));
     const int t = r->agg_types[k];
-    types.push_back(t == PH_AGG_COUNT ? "LONG" : ((t == PH_AGG_DISTINCTCOUNTHLL || t == PH_AGG_DISTINCTCOUNT) ? "OBJECT" : "DOUBLE"));
+    types.push_back(t == PH_AGG_COUNT ? "LONG" : ((t == PH_AGG_DISTINCTCOUNTHLL || t == PH_AGG_DISTINCTCOUNT || t == PH_AGG_PERCENTILE) ? "OBJECT" : "DOUBLE"));
     width[nk + k] = 8;
   }
   for (int c = 0; c < ncol; ++c) {
@@ -201,6 +231,35 @@ std::vector<uint8_t> result_to_datatable(const ph_result* r, const ph_query* q, 
         std::vector<uint32_t> w(words, 0);
         for (int j = 0; j < m; ++j) w[j / 6] |= (uint32_t)(reg[j] & 0x1f) << (5 * (j % 6));
         for (uint32_t x : w) var.i32((int32_t)x);
+      } else if (t == PH_AGG_PERCENTILE) {
+        // the DoubleArrayList of the matched values (ObjectSerDeUtils.java:328-357): int objectType 3, int size, the
+        // doubles -- each value of the row's histogram `count` times, ascending.  The reference writes arrival order
+        // and sorts at the broker, so this is the same multiset but not the same bytes (parity unpinned)
+        if (k >= (int)r->percentile.size() || !r->percentile[k].set) fail(PH_ERR_INVALID_ARGUMENT, "PERCENTILE result without a dictionary");
+        const ph_result::Percentile& d = r->percentile[k];
+        const uint32_t* cnt = reinterpret_cast<const uint32_t*>(base) + (size_t)g * (size_t)std::max<int64_t>(1, d.count);
+        uint64_t total = 0;
+        for (int64_t i = 0; i < d.count; ++i) total += cnt[i];
+        if (total > (uint64_t)INT32_MAX / 8 - 2) fail(PH_ERR_UNSUPPORTED, "PERCENTILE value list beyond one DataTable object");
+        const size_t start = var.b.size();
+        var.i32(3);  // ObjectSerDeUtils.ObjectType.DoubleArrayList
+        var.i32((int32_t)total);
+        for (int64_t i = 0; i < d.count; ++i) {
+          if (!cnt[i]) continue;
+          const uint8_t* v = d.values.data() + (size_t)d.entry_size * (size_t)i;
+          double x;
+          switch (d.data_type) {
+            case PH_INT: { int32_t y; memcpy(&y, v, 4); x = (double)y; break; }
+            case PH_LONG: { int64_t y; memcpy(&y, v, 8); x = (double)y; break; }
+            case PH_FLOAT: { float y; memcpy(&y, v, 4); x = (double)y; break; }
+            default: memcpy(&x, v, 8);
+          }
+          uint64_t bits;
+          memcpy(&bits, &x, 8);
+          for (uint32_t c = 0; c < cnt[i]; ++c) var.i64((int64_t)bits);
+        }
+        put_be(dst, (uint32_t)start, 4);
+        put_be(dst + 4, (uint32_t)(var.b.size() - start - 4), 4);
       } else if (t == PH_AGG_DISTINCTCOUNT) {
         // the value set convertToValueSet builds from the dictId bitmap (BaseDistinctAggregateAggregationFunction.java:
         // 77-108), serialised as ObjectSerDeUtils does (:725-891): int objectType, int size, the values (strings: int

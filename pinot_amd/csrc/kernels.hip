@@ -29,6 +29,10 @@ void launch_scan(const KParams& p, int mode, int ng, int rec64, int grid, size_t
     return;
   }
   PH_HIP_CHECK(hipGetLastError());  // a failure left by an earlier unchecked call is reported as such, not as ours
+  if (p.num_hist) {  // PERCENTILE: the scan's histogram variant (it carries the DISTINCTCOUNT insert of mixed queries)
+    launch_scan_hist(p, mode, ng, grid, lds, s);
+    return;
+  }
   if (p.num_dc) {  // DISTINCTCOUNT: the scan's bitset variant (the caller runs k_distinct_finish after its last launch)
     launch_scan_distinct(p, mode, ng, grid, lds, s);
     return;

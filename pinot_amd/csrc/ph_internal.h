@@ -365,6 +365,30 @@ struct KParams {
   int32_t dc_words[kMaxHll];      // ceil(result dictionary size / 32)
   uint32_t* out_dc;               // [num_groups][dc_row_words]
   int32_t* dc_counts;             // [num_groups][num_dc] popcounts, written by k_distinct_finish
+  // PERCENTILE histograms (scan_hist.hip; read by k_scan<.., LATE = 4> only).  Row g of out_hist is hist_row_words
+  // uint32 counters; slot h's histogram over its result dictionary is the hist_size[h] counters at hist_off[h].
+  int32_t num_hist;               // PERCENTILE slots (distinct columns); 0: the launch is not a PERCENTILE one
+  int32_t hist_lds;               // MODE_AGG / MODE_GROUP_LDS: the workgroup's histograms live in LDS at lds_hist_off
+  int32_t lds_hist_off;
+  int32_t hist_row_words;
+  int32_t hist_slot[kMaxHll];     // column slot of each PERCENTILE slot (its DevColumn::remap: dictId -> counter)
+  int32_t hist_off[kMaxHll];
+  uint32_t* out_hist;             // [num_groups][hist_row_words]
+};
+
+// k_percentile_finish (scan_hist.hip): one wave per (row, slot) of the histogram table; for every PERCENTILE
+// aggregation of the slot the result dictId of its rank (-1: an empty row)
+struct PctFinishParams {
+  const uint32_t* hist;           // [rows][row_words]
+  int32_t* ids;                   // [rows][num_aggs] result dictIds
+  int64_t rows;
+  int32_t row_words;
+  int32_t num_slots;
+  int32_t num_aggs;               // PERCENTILE aggregations of the query (<= kMaxAggs)
+  int32_t off[kMaxHll];           // slot h's counters in a row
+  int32_t size[kMaxHll];          // slot h's result dictionary size D_h
+  int32_t agg_slot[kMaxAggs];     // slot of PERCENTILE aggregation a
+  double agg_p[kMaxAggs];         // its percentile, 0..100
 };
 
 // Kernel B of the partitioned group-by: aggregates one batch of records per partition in LDS, then merges
@@ -802,6 +826,10 @@ void launch_scan_sketch(const KParams& p, int mode, int ng, int grid, size_t lds
 // k_distinct_finish: the popcount of every (row, slot) bitset of out_dc into dc_counts, `rows` result rows
 void launch_scan_distinct(const KParams& p, int mode, int ng, int grid, size_t lds, hipStream_t s);
 void launch_distinct_finish(const KParams& p, int64_t rows, hipStream_t s);
+// scan_hist.hip: the generic scan's PERCENTILE variant (a launch whose KParams::num_hist is set; it carries the
+// DISTINCTCOUNT insert too, for queries that mix both), and k_percentile_finish over the histogram table
+void launch_scan_hist(const KParams& p, int mode, int ng, int grid, size_t lds, hipStream_t s);
+void launch_percentile_finish(const PctFinishParams& f, hipStream_t s);
 
 void build_bitmap_directory(Column& c);  // at pin, from c.inverted
 // at pin: the (key, slice) container directory of an exact range index's RangeBitmap (after Pinot's 12-byte header)
@@ -999,6 +1027,16 @@ struct ph_result {
     std::vector<int32_t> counts;
   };
   std::vector<Distinct> distinct;  // per aggregation (set only for DISTINCTCOUNT)
+  // a PERCENTILE aggregation's rows are uint32[count] histograms over its result dictionary (laid out like Distinct's)
+  // and the rows' final values: the dictionary value of the dictId k_percentile_finish found, as double (-inf: empty)
+  struct Percentile {
+    bool set = false;
+    int32_t data_type = 0, entry_size = 0;
+    int64_t count = 0;
+    std::vector<uint8_t> values;
+    std::vector<double> finals;
+  };
+  std::vector<Percentile> percentile;  // per aggregation (set only for PERCENTILE)
   int64_t num_groups = 0;
   int32_t mode = 0;
   ph_exec_stats stats{};

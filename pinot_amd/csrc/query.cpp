@@ -1162,10 +1162,10 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
   // segments a star-tree serves (GroupByPlanNode.java:77-99, AggregationPlanNode.java:122-141): their views, merged
   // with the rest (startree.cpp)
   const std::map<const ph_segment*, StarSegPlan>* star = dn ? dn->star : nullptr;
-  // (a query holding a DISTINCTCOUNT is not served from a tree: it scans the segments' own docs)
+  // (a query holding a DISTINCTCOUNT or a PERCENTILE is not served from a tree: it scans the segments' own docs)
   bool any_distinct = false;
   for (int k = 0; k < q->num_aggregations && q->aggregations; ++k)
-    any_distinct |= q->aggregations[k].type == PH_AGG_DISTINCTCOUNT;
+    any_distinct |= q->aggregations[k].type == PH_AGG_DISTINCTCOUNT || q->aggregations[k].type == PH_AGG_PERCENTILE;
   if (!star && !fds && !q->skip_star_tree && nseg > 0 && !any_distinct)
     if (ph_result* r = star_tree_execute(ctx, q, segs_in, nseg, dop)) return r;
   PH_HIP_CHECK(hipSetDevice(ctx->device));
@@ -1212,13 +1212,16 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
   const int nagg = q->num_aggregations;
   int log2m = 0;
   // value terms: a column, or a 2-operand expression `val_cols[j] <op> val_cols2[j]`
-  std::vector<std::string> val_cols, val_cols2, hll_cols, dc_cols;
+  std::vector<std::string> val_cols, val_cols2, hll_cols, dc_cols, hs_cols;
   std::vector<int> val_ops, val_exprs;
-  std::vector<int> agg_val(nagg, -1), agg_hll(nagg, -1), agg_dc(nagg, -1);
+  std::vector<int> agg_val(nagg, -1), agg_hll(nagg, -1), agg_dc(nagg, -1), agg_hs(nagg, -1);
   std::set<std::string> projected(group_cols.begin(), group_cols.end());
   for (int k = 0; k < nagg; ++k) {
     const ph_aggregation& a = q->aggregations[k];
-    if (a.type < PH_AGG_COUNT || a.type > PH_AGG_DISTINCTCOUNT) fail(PH_ERR_UNSUPPORTED, "aggregation type");
+    if (a.type < PH_AGG_COUNT || a.type > PH_AGG_PERCENTILE) fail(PH_ERR_UNSUPPORTED, "aggregation type");
+    // parsePercentileToInt / parsePercentileToDouble (AggregationFunctionFactory.java:376-386); NaN fails the test too
+    if (a.type == PH_AGG_PERCENTILE && !(a.percentile >= 0.0 && a.percentile <= 100.0))
+      fail(PH_ERR_BAD_QUERY, "Invalid percentile: " + std::to_string(a.percentile));
     res->agg_types.push_back(a.type);
     const int lm = a.type == PH_AGG_DISTINCTCOUNTHLL ? (a.log2m > 0 ? a.log2m : 8) : 0;
     res->agg_log2m.push_back(lm);
@@ -1253,6 +1256,19 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
       }
       continue;
     }
+    if (a.type == PH_AGG_PERCENTILE) {
+      // a histogram slot per distinct column: every PERCENTILE of the column reads it; log2m / column2 are ignored
+      if (a.expr_op != PH_EXPR_NONE) fail(PH_ERR_UNSUPPORTED, "PERCENTILE of an expression");
+      auto it = std::find(hs_cols.begin(), hs_cols.end(), std::string(a.column));
+      if (it == hs_cols.end()) {
+        if ((int)hs_cols.size() >= kMaxHll) fail(PH_ERR_UNSUPPORTED, "too many PERCENTILE columns");
+        hs_cols.push_back(a.column);
+        agg_hs[k] = (int)hs_cols.size() - 1;
+      } else {
+        agg_hs[k] = (int)(it - hs_cols.begin());
+      }
+      continue;
+    }
     const int eop = a.expr_op;
     if (eop < PH_EXPR_NONE || eop > PH_EXPR_ADD) fail(PH_ERR_UNSUPPORTED, "expression operator");
     const std::string col2 = eop ? lit(a.column2) : std::string();
@@ -1276,10 +1292,20 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
     val_ops[j] |= a.type == PH_AGG_SUM ? 1 : (a.type == PH_AGG_MIN ? 2 : 4);
   }
   const int nvals = (int)val_cols.size(), num_hll = (int)hll_cols.size(), ndc = (int)dc_cols.size();
+  const int nhs = (int)hs_cols.size();
+  const int ntab = ndc + nhs;  // slots kept as per-row tables over a result dictionary: the generic scan only
   // DISTINCTCOUNT shapes the GPU path does not serve (the caller's CPU plan does)
   if (ndc) {
     if (dop) fail(PH_ERR_UNSUPPORTED, "DISTINCTCOUNT on dense partials");
     if (star) fail(PH_ERR_UNSUPPORTED, "DISTINCTCOUNT over a star-tree view");
+  }
+  // PERCENTILE: the same shapes, and what its uint32 counters and numeric result exclude
+  if (nhs) {
+    if (dop) fail(PH_ERR_UNSUPPORTED, "PERCENTILE on dense partials");
+    if (star) fail(PH_ERR_UNSUPPORTED, "PERCENTILE over a star-tree view");
+    int64_t docs = 0;
+    for (auto* s : segs) docs += s->num_docs;  // (checked non-null above)
+    if (docs >= (int64_t(1) << 32)) fail(PH_ERR_UNSUPPORTED, "PERCENTILE over 2^32 docs or more in one call");
   }
   if (q->filter_root >= 0)
     for (int i = 0; i < q->num_predicates; ++i) {
@@ -1405,6 +1431,46 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
     dc_row_words += dc_words[h];
   }
   if (dc_row_words >= (int64_t(1) << 30)) fail(PH_ERR_UNSUPPORTED, "DISTINCTCOUNT dictionaries too large for one bitset row");
+  // PERCENTILE slots: each one's result dictionary and its place in a histogram row (KParams::hist_*)
+  std::vector<std::shared_ptr<GlobalDict>> hs_dicts;
+  std::vector<int64_t> hs_size(nhs, 0), hs_off(nhs, 0);
+  int64_t hist_row_words = 0;
+  for (int h = 0; h < nhs; ++h) {
+    if (segs.empty()) fail(PH_ERR_UNSUPPORTED, "PERCENTILE without segments");
+    hs_dicts.push_back(column_dict(hs_cols[h]));
+    // (the result dictionary has the column's stored type: the one place a STRING column is refused)
+    if (hs_dicts[h]->dict.type == PH_STRING) fail(PH_ERR_UNSUPPORTED, "PERCENTILE on STRING column " + hs_cols[h]);
+    hs_size[h] = std::max<int64_t>(1, hs_dicts[h]->dict.size);
+    hs_off[h] = hist_row_words;
+    hist_row_words += hs_size[h];
+  }
+  if (hist_row_words >= (int64_t(1) << 30)) fail(PH_ERR_UNSUPPORTED, "PERCENTILE dictionaries too large for one histogram row");
+  int npct = 0;  // PERCENTILE aggregations, in query order: column a of k_percentile_finish's ids
+  std::vector<int> agg_pct(nagg, -1);
+  for (int k = 0; k < nagg; ++k)
+    if (agg_hs[k] >= 0) agg_pct[k] = npct++;
+  int32_t* pct_ids = nullptr;  // [table rows][npct] result dictIds (device)
+  // the result columns of the PERCENTILE aggregations besides their histogram rows (ph_result_percentile_*)
+  auto init_percentile_results = [&](int64_t rows) {
+    res->percentile.assign(nagg, ph_result::Percentile{});
+    for (int k = 0; k < nagg; ++k) {
+      if (agg_hs[k] < 0) continue;
+      const Dictionary& d = hs_dicts[agg_hs[k]]->dict;
+      ph_result::Percentile& o = res->percentile[k];
+      o.set = true;
+      o.data_type = d.type;
+      o.entry_size = key_entry_size(d);
+      o.count = d.size;
+      o.values.assign((size_t)o.entry_size * (size_t)d.size, 0);
+      for (int64_t i = 0; i < d.size; ++i) put_key_value(d, i, o.values.data() + (size_t)o.entry_size * i, o.entry_size);
+      o.finals.assign((size_t)rows, -INFINITY);
+    }
+  };
+  // the final value of a row: the dictionary value of the dictId k_percentile_finish found, converted to double last
+  auto percentile_final = [&](int k, int32_t id) -> double {
+    const Dictionary& d = hs_dicts[agg_hs[k]]->dict;
+    return (id < 0 || id >= d.size) ? -INFINITY : value_as_double(d, id);
+  };
   // the result columns of the DISTINCTCOUNT aggregations besides their bitset rows (ph_result_distinct_*)
   auto init_distinct_results = [&]() {
     res->distinct.assign(nagg, ph_result::Distinct{});
@@ -1424,7 +1490,9 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
 
   // ---- aggregation-only, no filter, metadata-answerable (NonScanBasedAggregationOperator)
   bool non_scan = q->filter_root < 0 && q->num_group_by == 0 && nagg > 0;
-  for (int k = 0; k < nagg && non_scan; ++k) non_scan = q->aggregations[k].type != PH_AGG_SUM;
+  // (PERCENTILE scans in the reference too: AggregationPlanNode's dictionary-based operator does not serve it)
+  for (int k = 0; k < nagg && non_scan; ++k)
+    non_scan = q->aggregations[k].type != PH_AGG_SUM && q->aggregations[k].type != PH_AGG_PERCENTILE;
   if (dop || star) non_scan = false;  // dense partials always come from the scan; a view's filter is its traversal
   res->num_groups = 1;
   auto init_row_results = [&](int64_t rows) {
@@ -1433,8 +1501,10 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
       const int t = q->aggregations[k].type;
       size_t w = t == PH_AGG_DISTINCTCOUNTHLL ? (size_t)(1 << res->agg_log2m[k]) : 8;
       if (t == PH_AGG_DISTINCTCOUNT) w = 4 * (size_t)dc_words[agg_dc[k]];  // uint32[W] bitset rows
+      if (t == PH_AGG_PERCENTILE) w = 4 * (size_t)hs_size[agg_hs[k]];      // uint32[D] histogram rows
       res->aggs[k].assign(w * rows, 0);
     }
+    if (nhs) init_percentile_results(rows);
     if (ndc) {
       init_distinct_results();
       for (int k = 0; k < nagg; ++k)
@@ -1832,6 +1902,12 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
     kp.hll_slot[h] = pl.slot.at(hll_cols[h]);
     kp.hll_words[h] = hll_words[h];
   }
+  kp.num_hist = nhs;
+  kp.hist_row_words = (int32_t)hist_row_words;
+  for (int h = 0; h < nhs; ++h) {
+    kp.hist_slot[h] = pl.slot.at(hs_cols[h]);
+    kp.hist_off[h] = (int32_t)hs_off[h];
+  }
   kp.num_dc = ndc;
   kp.dc_row_words = (int32_t)dc_row_words;
   for (int h = 0; h < ndc; ++h) {
@@ -1915,7 +1991,7 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
   float dev_ms = 0.f;
   // a plain group-by's scan completion, matched-doc count and limit flags are read at the compaction's sync
   // (one host round trip instead of three)
-  const bool defer_sync = q->num_group_by > 0 && num_hll == 0 && ndc == 0 && dop != DENSE_EXECUTE && !fin;
+  const bool defer_sync = q->num_group_by > 0 && num_hll == 0 && ntab == 0 && dop != DENSE_EXECUTE && !fin;
   std::unique_ptr<PinnedBlock> dsc;  // pinned: matched total, then 3 words per limit segment
   // the fused AND walks' sums (pinned, stream b): read at the end of the call, so the result compaction and copies
   // on the main stream overlap the walks instead of waiting behind them
@@ -1961,20 +2037,24 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
   int rec64 = 0;
   kp.stage_off = 0;
   if (q->num_group_by == 0) {
-    mode = (nvals == 0 && num_hll == 0 && ndc == 0) ? MODE_COUNT : MODE_AGG;
+    mode = (nvals == 0 && num_hll == 0 && ntab == 0) ? MODE_COUNT : MODE_AGG;
     kp.lds_hll_off = 0;
     lds_tables = (size_t)num_hll * (m ? m : 1) * 4 + 16;
     lds_tables_no_dc = lds_tables;
-    if (ndc) {
-      // the one row of DISTINCTCOUNT bitsets in LDS when it fits beside the HLL registers under the LDS table bound
-      // (option lds_table_max forces the HBM form), else straight in HBM
+    if (ntab) {
+      // the one row of DISTINCTCOUNT bitsets and PERCENTILE histograms in LDS when it fits beside the HLL registers
+      // under the LDS table bound (option lds_table_max forces the HBM form), else straight in HBM.  Both kinds of a
+      // mixed query take the same form
       size_t dc_max = 64 * 1024;
       if (ctx->has(OPT_LDS_TABLE_MAX)) dc_max = (size_t)std::max<int64_t>(0, ctx->opt(OPT_LDS_TABLE_MAX));
       const size_t off = (lds_tables + 15) / 16 * 16;
-      if (off + (size_t)dc_row_words * 4 <= dc_max) {
-        kp.dc_lds = 1;
+      const size_t hoff = (off + (size_t)dc_row_words * 4 + 15) / 16 * 16;
+      if (hoff + (size_t)hist_row_words * 4 <= dc_max) {
+        kp.dc_lds = ndc > 0;
         kp.lds_dc_off = (int32_t)off;
-        lds_tables = off + (size_t)dc_row_words * 4;
+        kp.hist_lds = nhs > 0;
+        kp.lds_hist_off = (int32_t)hoff;
+        lds_tables = hoff + (size_t)hist_row_words * 4;
       }
     }
   } else {
@@ -1998,7 +2078,13 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
       const double dcb = (double)G * (double)dc_row_words * 4.0;
       off = (dcb < 1e12 && off < SIZE_MAX / 4) ? off + (size_t)dcb : SIZE_MAX / 2;
     }
-    const bool part_ok = num_hll == 0 && ndc == 0 && nvals <= 1 && (nvals == 0 || (val_is_int[0] && !val_exprs[0] && vmax >= vmin &&
+    if (nhs) {  // the PERCENTILE histogram rows after them, under the same bound
+      off = off < SIZE_MAX / 4 ? (off + 15) / 16 * 16 : off;
+      kp.lds_hist_off = (int32_t)std::min<size_t>(off, INT32_MAX);
+      const double hb = (double)G * (double)hist_row_words * 4.0;
+      off = (hb < 1e12 && off < SIZE_MAX / 4) ? off + (size_t)hb : SIZE_MAX / 2;
+    }
+    const bool part_ok = num_hll == 0 && ntab == 0 && nvals <= 1 && (nvals == 0 || (val_is_int[0] && !val_exprs[0] && vmax >= vmin &&
                                                                        (uint64_t)(vmax - vmin) < (1ull << 32))) &&
                          G <= ((int64_t)kPartMaxParts << kPartKeysLog2) && !any_limit &&
                          !ctx->has(OPT_DISABLE_PARTITION);
@@ -2009,29 +2095,34 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
     // (38.8 vs 1.7 ms: the cache cannot hold every key, the rest pays device atomics)
     size_t lds_table_max = 64 * 1024;
     if (ctx->has(OPT_LDS_TABLE_MAX)) lds_table_max = (size_t)std::max<int64_t>(0, ctx->opt(OPT_LDS_TABLE_MAX));
-    const bool cache_ok = num_hll == 0 && ndc == 0 && nvals <= 1 && !ctx->has(OPT_NO_GROUP_CACHE);
+    const bool cache_ok = num_hll == 0 && ntab == 0 && nvals <= 1 && !ctx->has(OPT_NO_GROUP_CACHE);
     // (an explicit lds_table_max holds for every query: tests force the HBM table of a DISTINCTCOUNTHLL group-by)
     if (off <= ((cache_ok || ctx->has(OPT_LDS_TABLE_MAX)) ? lds_table_max : (size_t)64 * 1024)) {
       mode = MODE_GROUP_LDS;
       lds_tables = off;
       kp.dc_lds = ndc > 0;
+      kp.hist_lds = nhs > 0;
     } else if (part_ok && G >= 65536) {
       mode = MODE_PARTITION;
     } else {
       int nout = 1;  // 8-byte tables per group
       for (int j = 0; j < nvals; ++j) nout += __builtin_popcount(val_ops[j] & 7);
       const double bytes = (double)G * (8.0 * nout + 4.0 * num_hll * (m ? m : 1));
-      if (ndc) {
-        // DISTINCTCOUNT runs on the dense tables only (no hash table of bitset rows).  Its budget counts the device
-        // table and the host copy of the rows that can be non-empty: at most one per scanned doc
-        if (bytes > kDenseTableBudget)
-          fail(PH_ERR_UNSUPPORTED, "DISTINCTCOUNT over a group key space beyond the dense tables");
+      if (ntab) {
+        // DISTINCTCOUNT and PERCENTILE run on the dense tables only (no hash table of bitset / histogram rows).  Their
+        // budget counts the device table and the host copy of the rows that can be non-empty: at most one per scanned
+        // doc.  A bitset row is 1 bit per value, a histogram row 4 bytes per value; the DISTINCTCOUNT rows of a mixed
+        // query count towards the PERCENTILE check
         int64_t live_docs = 0;
         for (int i = 0; i < nseg; ++i)
           if (seg_live[i]) live_docs += segs[i]->num_docs;
-        const double row_bytes = 4.0 * (double)dc_row_words;
-        if (bytes + (double)G * row_bytes + (double)std::min<int64_t>(G, live_docs) * row_bytes > kDenseTableBudget)
-          fail(PH_ERR_UNSUPPORTED, "DISTINCTCOUNT bitset table exceeds the dense table budget");
+        auto table_budget = [&](const std::string& fn, const char* table, double row_bytes) {
+          if (bytes > kDenseTableBudget) fail(PH_ERR_UNSUPPORTED, fn + " over a group key space beyond the dense tables");
+          if (bytes + (double)G * row_bytes + (double)std::min<int64_t>(G, live_docs) * row_bytes > kDenseTableBudget)
+            fail(PH_ERR_UNSUPPORTED, fn + " " + table + " table exceeds the dense table budget");
+        };
+        if (ndc) table_budget("DISTINCTCOUNT", "bitset", 4.0 * (double)dc_row_words);
+        if (nhs) table_budget("PERCENTILE", "histogram", 4.0 * ((double)hist_row_words + (double)dc_row_words));
       }
       if (bytes <= kDenseTableBudget) {
         mode = MODE_GROUP_GLOBAL;
@@ -2085,6 +2176,7 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
   int tix = 0;
   const int64_t hll_table_words = TR * num_hll * (m ? m : 1);
   const int64_t dc_table_words = TR * dc_row_words;
+  const int64_t hist_table_words = TR * hist_row_words;
   kp.out_count = reinterpret_cast<unsigned long long*>(out_table(tix, 8 * (size_t)TR));
   for (int j = 0; j < nvals; ++j) {
     if (val_ops[j] & 1) kp.out_sum[j] = out_table(tix, 8 * (size_t)TR);
@@ -2100,6 +2192,10 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
     kp.out_dc = scratch.alloc<uint32_t>((size_t)dc_table_words);
     kp.dc_counts = scratch.alloc<int32_t>((size_t)TR * ndc);
   }
+  if (nhs) {
+    kp.out_hist = scratch.alloc<uint32_t>((size_t)hist_table_words);
+    pct_ids = scratch.alloc<int32_t>((size_t)TR * npct);
+  }
   // identities of every output table (again before a numGroupsLimit rescan)
   auto init_tables = [&]() {
     PH_HIP_CHECK(hipMemsetAsync(kp.out_count, 0, sizeof(unsigned long long) * TR, st));
@@ -2113,6 +2209,10 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
     if (ndc) {  // the scan's inserts only set bits: the table starts from zero, on the scan's stream
       PH_HIP_CHECK(hipMemsetAsync(kp.out_dc, 0, 4 * (size_t)dc_table_words, st));
       PH_HIP_CHECK(hipMemsetAsync(kp.dc_counts, 0, 4 * (size_t)TR * ndc, st));
+    }
+    if (nhs) {  // the scan only adds: the histograms start from zero, on the scan's stream
+      PH_HIP_CHECK(hipMemsetAsync(kp.out_hist, 0, 4 * (size_t)hist_table_words, st));
+      PH_HIP_CHECK(hipMemsetAsync(pct_ids, 0xFF, 4 * (size_t)TR * npct, st));
     }
   };
   init_tables();
@@ -2137,7 +2237,7 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
   // leaves' densities multiplied: an independence estimate) -> gather the matched docs instead of streaming every
   // referenced column
   bool sparse_plan = false;
-  if ((mode == MODE_GROUP_LDS || mode == MODE_GROUP_GLOBAL) && num_hll == 0 && ndc == 0 && nvals <= 1 && q->num_group_by > 0) {
+  if ((mode == MODE_GROUP_LDS || mode == MODE_GROUP_GLOBAL) && num_hll == 0 && ntab == 0 && nvals <= 1 && q->num_group_by > 0) {
     bool ok = true;
     double docs = 0, hits = 0;
     for (int i = 0; i < nseg && ok; ++i) {
@@ -2167,7 +2267,7 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
   // k_agg_sparse over ANDs of scan leaves only (register-direct leaves, then gathers of the matched docs' values):
   // aggregation-only queries whose every segment's AND keeps < 1/8 of the docs (same estimate as above)
   bool agg_conj = false;
-  if (mode == MODE_AGG && ndc == 0 && nvals >= 1 && (nvals == 1 || std::none_of(val_exprs.begin(), val_exprs.end(), [](int x) { return x != 0; }))) {
+  if (mode == MODE_AGG && ntab == 0 && nvals >= 1 && (nvals == 1 || std::none_of(val_exprs.begin(), val_exprs.end(), [](int x) { return x != 0; }))) {
     bool ok = true;
     double docs = 0, hits = 0;
     for (int i = 0; i < nseg && ok; ++i) {
@@ -2320,6 +2420,9 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
     // same dictionary, so the same remap)
     for (int h = 0; h < ndc; ++h)
       d.cols[kp.dc_slot[h]].remap = segment_remap(ctx, *s, *s->columns.at(dc_cols[h]), *dc_dicts[h]);
+    // PERCENTILE: dictId -> counter of the slot's result dictionary, the same way
+    for (int h = 0; h < nhs; ++h)
+      d.cols[kp.hist_slot[h]].remap = segment_remap(ctx, *s, *s->columns.at(hs_cols[h]), *hs_dicts[h]);
     for (int h = 0; h < num_hll; ++h) {
       Column& hc = *s->columns.at(hll_cols[h]);
       if (hll_words[h]) {
@@ -2394,7 +2497,7 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
     }
     agg_sparse_plan = (all_bitmap_agg && hits * 8 < docs) || agg_conj;
     if (ctx->has(OPT_AGG_SPARSE)) agg_sparse_plan = (all_bitmap_agg || agg_conj) && ctx->opt(OPT_AGG_SPARSE) != 0;
-    if (any_sketch || ndc) agg_sparse_plan = false;  // (DISTINCTCOUNT bitsets: the generic scan only)
+    if (any_sketch || ntab) agg_sparse_plan = false;  // (DISTINCTCOUNT bitsets, PERCENTILE histograms: the generic scan only)
   }
   const bool agg_cont_plan = cont_defer && agg_sparse_plan && all_bitmap_agg && !agg_conj;
   int64_t chunk_docs_total = 0;  // the streaming chunk list's words x 64 and its widest chunk
@@ -2449,7 +2552,7 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
       while (tw > 4 && stage(tw) + lds_tables > 160 * 1024) tw /= 2;
       if (stage(tw) + lds_tables > 160 * 1024) fail(PH_ERR_UNSUPPORTED, "LDS group table and staging exceed 160 KiB");
     }
-    if (mode == MODE_AGG && kp.dc_lds) {
+    if (mode == MODE_AGG && (kp.dc_lds || kp.hist_lds)) {
       // an lds_table_max above the default can admit a bitset row that does not fit beside the staging areas in one
       // CU's 160 KiB: the HBM form then (the tile stays as every other MODE_AGG query's)
       size_t b = 0;
@@ -2457,6 +2560,8 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
       if ((size_t)kWaves * std::max<size_t>(16, b) + lds_tables > 160 * 1024) {
         kp.dc_lds = 0;
         kp.lds_dc_off = 0;
+        kp.hist_lds = 0;
+        kp.lds_hist_off = 0;
         lds_tables = lds_tables_no_dc;
       }
     }
@@ -2472,7 +2577,7 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
   // a decode that gathers (bitset / bitmap / program filters, key remaps, dictionary values, HLL tables)
   // would wait behind an early prefetch
   for (auto& d : dsegs) {
-    bool g = d.fkind == FK_SET || d.fkind == FK_BITMAP || d.fkind == FK_GENERIC || num_hll > 0 || ndc > 0;
+    bool g = d.fkind == FK_SET || d.fkind == FK_BITMAP || d.fkind == FK_GENERIC || num_hll > 0 || ntab > 0;
     for (int k = 0; d.fkind == FK_CONJ && k < d.nconj; ++k) g |= d.cset[k] != nullptr || d.clen[k] == 0;
     for (int gi = 0; gi < q->num_group_by; ++gi) g |= d.cols[kp.group_slot[gi]].remap != nullptr;
     for (int j = 0; j < nvals; ++j) g |= d.vals[j].kind != VK_PACKED || (val_exprs[j] && d.vals2[j].kind != VK_PACKED);
@@ -2534,7 +2639,7 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
   // leaves; its 32-bit tile sums need value offsets below 2^26
   //   r3: also FK_CONJ ANDs of range leaves (no applyAnd statistic to count) and integer 2-operand value terms of
   //   two packed columns (per-doc int64 fold; SSB Q1.x)
-  kp.agg_fast = mode == MODE_AGG && nvals == 1 && num_hll == 0 && ndc == 0 && val_is_int[0] && !kp.late_prefetch &&
+  kp.agg_fast = mode == MODE_AGG && nvals == 1 && num_hll == 0 && ntab == 0 && val_is_int[0] && !kp.late_prefetch &&
                 !ctx->has(OPT_AGG_GENERIC);
   for (auto& d : dsegs) {
     if (!kp.agg_fast) break;  // (val_exprs is empty without value columns)
@@ -2547,7 +2652,7 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
   }
   // the lean LDS group-by (k_group_lds_lean): identity remaps, at most one packed integer value column whose
   // offsets from the table-wide minimum fit 32 bits, ALL / RANGE / DOCRANGE leaves
-  kp.lds_fast = mode == MODE_GROUP_LDS && num_hll == 0 && ndc == 0 && nvals <= 1 && !kp.late_prefetch &&
+  kp.lds_fast = mode == MODE_GROUP_LDS && num_hll == 0 && ntab == 0 && nvals <= 1 && !kp.late_prefetch &&
                 !ctx->has(OPT_LDS_GENERIC);
   if (nvals == 1)
     kp.lds_fast = kp.lds_fast && val_is_int[0] && !val_exprs[0] && vmax >= vmin && (uint64_t)(vmax - vmin) < (1ull << 32);
@@ -2618,6 +2723,7 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
     kp.lds_cnt_off += (int32_t)stage_bytes;
     kp.lds_hll_off += (int32_t)stage_bytes;
     kp.lds_dc_off += (int32_t)stage_bytes;
+    kp.lds_hist_off += (int32_t)stage_bytes;
     kp.gc_key_off += (int32_t)stage_bytes;
     for (int j = 0; j < nvals; ++j) {
       kp.lds_sum_off[j] += (int32_t)stage_bytes;
@@ -2934,6 +3040,7 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
                           : kp.group_sparse ? PH_KERNEL_GROUP_SPARSE
                           : kp.group_reg  ? PH_KERNEL_GROUP_REG
                           : kp.lds_fast  ? PH_KERNEL_GROUP_LDS_LEAN
+                          : nhs          ? (kp.hist_lds ? PH_KERNEL_SCAN_HIST_LDS : PH_KERNEL_SCAN_HIST_HBM)
                           : ndc          ? (kp.dc_lds ? PH_KERNEL_SCAN_DISTINCT_LDS : PH_KERNEL_SCAN_DISTINCT_HBM)
                                          : PH_KERNEL_SCAN;
       // device_ms opens here: it covers the numGroupsLimit pass and (below) the bitmap build too
@@ -3080,6 +3187,25 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
       }
       if (!scanned) run_scan(kp);
       if (ndc) launch_distinct_finish(kp, TR, st);  // the rows' popcounts, behind the last scan launch
+      if (nhs) {  // the rows' rank dictIds, one column per PERCENTILE aggregation
+        PctFinishParams fp{};
+        fp.hist = kp.out_hist;
+        fp.ids = pct_ids;
+        fp.rows = TR;
+        fp.row_words = (int32_t)hist_row_words;
+        fp.num_slots = nhs;
+        fp.num_aggs = npct;
+        for (int h = 0; h < nhs; ++h) {
+          fp.off[h] = (int32_t)hs_off[h];
+          fp.size[h] = (int32_t)hs_size[h];
+        }
+        for (int k = 0; k < nagg; ++k)
+          if (agg_pct[k] >= 0) {
+            fp.agg_slot[agg_pct[k]] = agg_hs[k];
+            fp.agg_p[agg_pct[k]] = q->aggregations[k].percentile;
+          }
+        launch_percentile_finish(fp, st);
+      }
       PH_HIP_CHECK(hipEventRecord(lane.lane->ev_stop, st));
     } else {
       // ---- partitioned group-by: batches of chunks; kernel A (filter + decode + partition) on `st`,
@@ -3613,6 +3739,7 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
       const int t = q->aggregations[k].type;
       need += t == PH_AGG_COUNT ? 0 : (t == PH_AGG_DISTINCTCOUNTHLL ? 4 * (size_t)m : 8);
       if (t == PH_AGG_DISTINCTCOUNT) need += 4 * (size_t)dc_words[agg_dc[k]];  // the bitset, then its count (8 bytes)
+      if (t == PH_AGG_PERCENTILE) need += 4 * (size_t)hs_size[agg_hs[k]];      // the histogram, then its dictId (8 bytes)
     }
     PinnedBlock blk_hold(ctx, st, need);
     uint8_t* blk = blk_hold.as<uint8_t>();
@@ -3625,6 +3752,10 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
         const int h = agg_dc[k];
         PH_HIP_CHECK(hipMemcpyAsync(blk + at[k], kp.out_dc + dc_off[h], 4 * (size_t)dc_words[h], hipMemcpyDeviceToHost, st));
         PH_HIP_CHECK(hipMemcpyAsync(blk + at[k] + 4 * (size_t)dc_words[h], kp.dc_counts + h, 4, hipMemcpyDeviceToHost, st));
+      } else if (t == PH_AGG_PERCENTILE) {
+        const int h = agg_hs[k];
+        PH_HIP_CHECK(hipMemcpyAsync(blk + at[k], kp.out_hist + hs_off[h], 4 * (size_t)hs_size[h], hipMemcpyDeviceToHost, st));
+        PH_HIP_CHECK(hipMemcpyAsync(blk + at[k] + 4 * (size_t)hs_size[h], pct_ids + agg_pct[k], 4, hipMemcpyDeviceToHost, st));
       } else if (t != PH_AGG_COUNT)
         PH_HIP_CHECK(hipMemcpyAsync(blk + at[k], src_of(k), 8, hipMemcpyDeviceToHost, st));
     }
@@ -3646,6 +3777,12 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
         const size_t wb = 4 * (size_t)dc_words[agg_dc[k]];
         memcpy(dst, blk + at[k], wb);
         memcpy(res->distinct[k].counts.data(), blk + at[k] + wb, 4);
+      } else if (t == PH_AGG_PERCENTILE) {
+        const size_t hb = 4 * (size_t)hs_size[agg_hs[k]];
+        memcpy(dst, blk + at[k], hb);
+        int32_t id;
+        memcpy(&id, blk + at[k] + hb, 4);
+        res->percentile[k].finals[0] = percentile_final(k, id);
       } else {
         int64_t raw;
         memcpy(&raw, blk + at[k], 8);
@@ -3654,7 +3791,7 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
       }
     }
 
-  } else if (num_hll == 0 && ndc == 0) {
+  } else if (num_hll == 0 && ntab == 0) {
     // device-side compaction: non-empty groups in key order, keys decoded, values converted to double,
     // copied straight into pinned result columns
     CompactParams cp{};
@@ -3798,6 +3935,7 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
     std::map<void*, std::vector<int64_t>> fetched;
     std::vector<uint32_t> regs;
     std::vector<int32_t> dcnt;  // [RG][ndc] DISTINCTCOUNT popcounts (k_distinct_finish)
+    std::vector<int32_t> pids;  // [RG][npct] PERCENTILE result dictIds (k_percentile_finish)
     for (int k = 0; k < nagg; ++k) {
       const int t = q->aggregations[k].type;
       uint8_t* dst = res->aggs[k].data();
@@ -3839,6 +3977,32 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
             const size_t W = (size_t)dc_words[h];
             memcpy(res->aggs[k2].data() + 4 * W * (size_t)r, slab.data() + (size_t)(g - s0) * RW + dc_off[h], 4 * W);
             res->distinct[k2].counts[(size_t)r] = dcnt[(size_t)g * ndc + h];
+          }
+        }
+      } else if (t == PH_AGG_PERCENTILE) {
+        // the non-empty rows' histograms and device-found dictIds, read in slabs of rows like the bitsets: one walk
+        // over the table at the first PERCENTILE fills every PERCENTILE aggregation of the query
+        if (!pids.empty()) continue;
+        pids.resize((size_t)RG * npct);
+        PH_HIP_CHECK(hipMemcpy(pids.data(), pct_ids, 4 * pids.size(), hipMemcpyDeviceToHost));
+        const size_t RW = (size_t)hist_row_words;
+        const int64_t slab_rows = std::max<int64_t>(1, (int64_t)((size_t(64) << 20) / (4 * RW)));
+        std::vector<uint32_t> slab;
+        int64_t s0 = -1;
+        for (int64_t r = 0; r < R; ++r) {
+          const int64_t g = live[r];
+          if (s0 < 0 || g >= s0 + slab_rows) {
+            s0 = g;
+            const int64_t nr = std::min<int64_t>(slab_rows, RG - s0);
+            slab.resize((size_t)nr * RW);
+            PH_HIP_CHECK(hipMemcpy(slab.data(), kp.out_hist + (size_t)s0 * RW, 4 * slab.size(), hipMemcpyDeviceToHost));
+          }
+          for (int k2 = k; k2 < nagg; ++k2) {
+            if (q->aggregations[k2].type != PH_AGG_PERCENTILE) continue;
+            const int h = agg_hs[k2];
+            const size_t D = (size_t)hs_size[h];
+            memcpy(res->aggs[k2].data() + 4 * D * (size_t)r, slab.data() + (size_t)(g - s0) * RW + hs_off[h], 4 * D);
+            res->percentile[k2].finals[(size_t)r] = percentile_final(k2, pids[(size_t)g * npct + agg_pct[k2]]);
           }
         }
       } else {

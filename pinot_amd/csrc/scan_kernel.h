@@ -525,6 +525,80 @@ __device__ __forceinline__ void distinct_lds_flush(const KParams& p, uint8_t* sm
   }
 }
 
+// ------------------------------------------------------------------ PERCENTILE histograms (k_scan<.., LATE = 4>)
+// The reference appends every matched value to a DoubleArrayList per result holder and sorts it at the end
+// (PercentileAggregationFunction.java:77-94, 146-158); here a result row holds, per PERCENTILE slot h, a histogram over
+// the slot's result dictionary: row g is counters [g * hist_row_words, (g + 1) * hist_row_words) of the table and value
+// i of slot h's dictionary is counter hist_off[h] + i -- the DISTINCTCOUNT layout with a uint32 counter for the bit.
+// The table lives in LDS (KParams::hist_lds; flushed once per workgroup) or in HBM.  There is no test before set: every
+// matched doc adds, so the hot value of a skewed column is one contended address.  LDS privatises it per workgroup; in
+// HBM the lanes of a wave that hold the same counter elect one lane to add their number (two rounds: the first active
+// lane's counter, then the first remaining lane's; what is left adds 1 each), so a wave sends one add for its hot value.
+// The round count is a guess, not a measured optimum: each round costs two ballots and a shuffle per slot whether the
+// column is skewed or not; DESIGN.md ("Percentile histograms") has the uniform and skewed timings of this form.
+__device__ __forceinline__ uint32_t* hist_lds_table(const KParams& p, uint8_t* smem) {
+  return reinterpret_cast<uint32_t*>(smem + p.lds_hist_off);
+}
+
+template <int MODE>
+__device__ __forceinline__ void hist_insert(const KParams& p, SegPtr S, uint8_t* smem, uint32_t doc, int64_t g) {
+#pragma unroll
+  for (int h = 0; h < kMaxHll; ++h) {
+    if (h >= p.num_hist) continue;
+    ColRef col = S->cols[p.hist_slot[h]];
+    uint32_t id = unpack_col(col, doc);
+    if (col.remap) id = (uint32_t)gld(col.remap + id);  // dictId -> result dictionary (nullptr: they are equal)
+    const int64_t ci = g * p.hist_row_words + p.hist_off[h] + (int64_t)id;
+    if (MODE != MODE_GROUP_GLOBAL && p.hist_lds) {
+      (void)__hip_atomic_fetch_add(hist_lds_table(p, smem) + ci, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    } else {
+      // the active lanes are the matched docs of this 64-doc word that reached the insert
+      const int lane = threadIdx.x & 63;
+      uint32_t add = 1u;
+      bool mine = true;  // this lane still owes its add
+#pragma unroll
+      for (int round = 0; round < 2; ++round) {
+        const unsigned long long todo = __ballot(mine);
+        if (!todo) break;
+        const int leader = __ffsll((long long)todo) - 1;
+        const int64_t lk = __shfl(ci, leader, 64);
+        const bool same = mine && ci == lk;
+        const unsigned long long peers = __ballot(same);
+        if (same) {
+          mine = lane == leader;
+          add = (uint32_t)__popcll(peers);
+        }
+        if (lane == leader) {
+          (void)__hip_atomic_fetch_add(p.out_hist + ci, add, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          mine = false;
+        }
+      }
+      if (mine) (void)__hip_atomic_fetch_add(p.out_hist + ci, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+}
+
+// the workgroup's LDS histograms: zeroed before the scan (followed by the kernel's barrier) ...
+template <int MODE>
+__device__ __forceinline__ void hist_lds_clear(const KParams& p, uint8_t* smem) {
+  if (MODE == MODE_GROUP_GLOBAL || !p.hist_lds) return;
+  const int64_t n = (MODE == MODE_GROUP_LDS ? p.num_groups : 1) * p.hist_row_words;
+  uint32_t* t = hist_lds_table(p, smem);
+  for (int64_t i = threadIdx.x; i < n; i += kBlock) t[i] = 0;
+}
+// ... and added into the HBM table after it: non-zero counters only, no value returned
+template <int MODE>
+__device__ __forceinline__ void hist_lds_flush(const KParams& p, uint8_t* smem) {
+  if (MODE == MODE_GROUP_GLOBAL || !p.hist_lds) return;
+  __syncthreads();
+  const int64_t n = (MODE == MODE_GROUP_LDS ? p.num_groups : 1) * p.hist_row_words;
+  const uint32_t* t = hist_lds_table(p, smem);
+  for (int64_t i = threadIdx.x; i < n; i += kBlock) {
+    const uint32_t x = t[i];
+    if (x) (void)__hip_atomic_fetch_add(p.out_hist + i, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
 // One staged tile of one segment: every parameter the inner loop needs is hoisted into (scalar) registers
 // once per tile, and the filter kind is a template parameter, so the per-64-doc body is LDS reads + ALU.
 template <int MODE, int NG, int REC64, int FK, int LATE>
@@ -791,8 +865,10 @@ __device__ __forceinline__ void process_tile(const KParams& p, SegPtr S, uint8_t
         if (MODE == MODE_GROUP_GLOBAL || MODE == MODE_GROUP_HASH) atomicMax(&p.out_hll[ri], e & 0xffu);  // g: slot
         else atomicMax(&lds_hll[ri], e & 0xffu);
       }
-      // DISTINCTCOUNT (scan_distinct.hip): only LATE == 3 carries the insert
-      if constexpr (LATE == 3) distinct_insert<MODE>(p, S, smem, doc, g);
+      // DISTINCTCOUNT (scan_distinct.hip): only LATE == 3 carries the insert -- and LATE == 4 (scan_hist.hip), the
+      // PERCENTILE variant, beside its histogram add (num_dc may be 0 there)
+      if constexpr (LATE == 3 || LATE == 4) distinct_insert<MODE>(p, S, smem, doc, g);
+      if constexpr (LATE == 4) hist_insert<MODE>(p, S, smem, doc, g);
     }
   };
 
@@ -900,7 +976,8 @@ __device__ __forceinline__ void process_tile(const KParams& p, SegPtr S, uint8_t
 // LATE: 0 = the next tile's loads are issued before this tile's decode, 1 = after it (a decode that gathers), 2 = 1
 // with DISTINCTCOUNTHLL slots that read star-tree sketch columns (scan_hll_sketch.hip; only sketch queries
 // instantiate it, so no other query carries the append), 3 = 1 with DISTINCTCOUNT bitset slots (scan_distinct.hip; only
-// DISTINCTCOUNT queries instantiate it, so no other query carries the insert, the LDS clear or the flush).
+// DISTINCTCOUNT queries instantiate it, so no other query carries the insert, the LDS clear or the flush), 4 = 3 with
+// PERCENTILE histogram slots (scan_hist.hip; only PERCENTILE queries instantiate it; num_dc may be 0).
 // Persistent grid over the chunk list.  A chunk (<= 256 words of one segment) is processed in rounds: in
 // round r wave w takes tile r * kWaves + w.  Rounds are workgroup-uniform (MODE_PARTITION flushes at round
 // boundaries with workgroup barriers); the other modes never synchronise inside the loop.
@@ -956,7 +1033,8 @@ __global__ void __launch_bounds__(MODE == MODE_PARTITION ? kPartBlock : kBlock) 
     uint32_t* words = reinterpret_cast<uint32_t*>(smem + p.pl_lcnt_off);
     for (int i = threadIdx.x; i < p.num_parts; i += BLOCK) words[i] = 0;
   }
-  if constexpr (LATE == 3) distinct_lds_clear<MODE>(p, smem);
+  if constexpr (LATE == 3 || LATE == 4) distinct_lds_clear<MODE>(p, smem);
+  if constexpr (LATE == 4) hist_lds_clear<MODE>(p, smem);
   __syncthreads();
 
   ScanAcc acc;
@@ -1146,7 +1224,8 @@ __global__ void __launch_bounds__(MODE == MODE_PARTITION ? kPartBlock : kBlock) 
       }
     }
   }
-  if constexpr (LATE == 3) distinct_lds_flush<MODE>(p, smem);
+  if constexpr (LATE == 3 || LATE == 4) distinct_lds_flush<MODE>(p, smem);
+  if constexpr (LATE == 4) hist_lds_flush<MODE>(p, smem);
   __syncthreads();
   if (threadIdx.x == 0 && s_matched && (MODE == MODE_COUNT || MODE == MODE_AGG))
     atomicAdd(&p.out_count[0], s_matched);

@@ -6,7 +6,8 @@ dictionary, DataSchema.fromBytes, fixed-size rows, variable-size data, metadata 
 ``reduce_datatables`` is the broker's merge of several servers' tables for this path:
 GroupByDataTableReducer.reduceAndSetResults (core/query/reduce/GroupByDataTableReducer.java:99) /
 AggregationDataTableReducer -- intermediate results merged per group key with AggregationFunction.merge
-(COUNT / SUM add, MIN / MAX, DISTINCTCOUNTHLL HyperLogLog.addAll = register max, DISTINCTCOUNT set union), then the final results, ORDER BY
+(COUNT / SUM add, MIN / MAX, DISTINCTCOUNTHLL HyperLogLog.addAll = register max, DISTINCTCOUNT set union, PERCENTILE
+DoubleArrayList.addAll), then the final results, ORDER BY
 and LIMIT (pinot_amd.reduce.reduce_groups).
 """
 from __future__ import annotations
@@ -17,8 +18,8 @@ from typing import Any, Dict, List, Sequence
 
 import numpy as np
 
-from .query import COUNT, DISTINCTCOUNT, DISTINCTCOUNTHLL, MAX, MIN, SUM, QueryContext
-from .reduce import ResultTable, merge_intermediate, reduce_groups
+from .query import COUNT, DISTINCTCOUNT, DISTINCTCOUNTHLL, MAX, MIN, PERCENTILE, SUM, QueryContext
+from .reduce import ResultTable, ValueCounts, merge_intermediate, reduce_groups
 
 # MetadataKey id -> (name, value type) (DataTable.java:103-137); "I" int, "L" long, "S" string
 METADATA_KEYS = {1: ("table", "S"), 2: ("numDocsScanned", "L"), 3: ("numEntriesScannedInFilter", "L"),
@@ -38,6 +39,7 @@ METADATA_KEYS = {1: ("table", "S"), 2: ("numDocsScanned", "L"), 3: ("numEntriesS
 HLL_OBJECT_TYPE = 6  # ObjectSerDeUtils.ObjectType.HyperLogLog
 # the value sets of DISTINCTCOUNT by stored type (ObjectSerDeUtils.java:113-123)
 SET_OBJECT_TYPES = {9: "INT", 15: "LONG", 16: "FLOAT", 17: "DOUBLE", 18: "STRING"}
+DOUBLE_LIST_OBJECT_TYPE = 3  # ObjectSerDeUtils.ObjectType.DoubleArrayList: PERCENTILE's matched values
 
 
 @dataclass
@@ -108,6 +110,20 @@ def set_deserialize(otype: int, b: bytes) -> frozenset:
     if p != len(b):
         raise ValueError(f"{data_type} set of {n} values takes {p} bytes, the object has {len(b)}")
     return frozenset(out)
+
+
+def double_list_deserialize(b: bytes) -> ValueCounts:
+    """A PERCENTILE value list from ObjectSerDeUtils bytes (DoubleArrayList deserializer, ObjectSerDeUtils.java:
+    328-357): int32 BE size, then the doubles BE in any order."""
+    if len(b) < 4:
+        raise ValueError(f"DoubleArrayList of {len(b)} bytes")
+    n = struct.unpack_from(">i", b, 0)[0]
+    if n < 0:
+        raise ValueError(f"DoubleArrayList of size {n}")
+    # the object's length is exactly its serialisation's (the reader slices it to that: DataTableImplV4.java:292-300)
+    if 4 + 8 * n != len(b):
+        raise ValueError(f"DoubleArrayList of {n} values takes {4 + 8 * n} bytes, the object has {len(b)}")
+    return ValueCounts.of(np.frombuffer(b, ">f8", n, 4).astype(np.float64))
 
 
 def decode(buf: bytes) -> DataTable:
@@ -197,6 +213,10 @@ def reduce_datatables(q: QueryContext, tables: Sequence[DataTable]) -> ResultTab
                     v = hll_deserialize(payload)[1]
                 elif a.function == DISTINCTCOUNT:
                     v = set_deserialize(*v)
+                elif a.function == PERCENTILE:
+                    otype, payload = v
+                    assert otype == DOUBLE_LIST_OBJECT_TYPE
+                    v = double_list_deserialize(payload)
                 inter.append(v)
             if key in groups:
                 groups[key] = [_merge(a.function, x, y) for a, x, y in zip(q.aggregations, groups[key], inter)]

@@ -134,6 +134,9 @@ class DistributedQuery:
         if any(a.function == "DISTINCTCOUNT" for a in q.aggregations):
             from .native import PH_ERR_UNSUPPORTED, UnsupportedError
             raise UnsupportedError(PH_ERR_UNSUPPORTED, "DISTINCTCOUNT on dense partials")
+        if any(a.function == "PERCENTILE" for a in q.aggregations):
+            from .native import PH_ERR_UNSUPPORTED, UnsupportedError
+            raise UnsupportedError(PH_ERR_UNSUPPORTED, "PERCENTILE on dense partials")
         import torch
         dev = torch.device("cuda", self.ctx.device)
         # run the library on torch's current stream so RCCL and the scan are ordered without host syncs

@@ -18,12 +18,14 @@ from typing import List, Sequence
 import numpy as np
 
 from . import native as N
-from .query import (COUNT, DISTINCTCOUNT, DISTINCTCOUNTHLL, MAX, MIN, SUM, FilterContext, QueryContext, parse_sql)
-from .reduce import ResultTable, reduce_groups
+from .query import (COUNT, DISTINCTCOUNT, DISTINCTCOUNTHLL, MAX, MIN, PERCENTILE, SUM, FilterContext, QueryContext,
+                    parse_sql)
+from .reduce import ResultTable, ValueCounts, reduce_groups
 from .segment import PinnedSegment, SegmentBuffers
 
 _AGG = {COUNT: N.PH_AGG_COUNT, SUM: N.PH_AGG_SUM, MIN: N.PH_AGG_MIN, MAX: N.PH_AGG_MAX,
-        DISTINCTCOUNTHLL: N.PH_AGG_DISTINCTCOUNTHLL, DISTINCTCOUNT: N.PH_AGG_DISTINCTCOUNT}
+        DISTINCTCOUNTHLL: N.PH_AGG_DISTINCTCOUNTHLL, DISTINCTCOUNT: N.PH_AGG_DISTINCTCOUNT,
+        PERCENTILE: N.PH_AGG_PERCENTILE}
 _PRED = {"EQ": N.PH_PRED_EQ, "NOT_EQ": N.PH_PRED_NOT_EQ, "IN": N.PH_PRED_IN, "NOT_IN": N.PH_PRED_NOT_IN,
          "RANGE": N.PH_PRED_RANGE}
 
@@ -56,7 +58,8 @@ SCAN_KERNEL_NAMES = {0: "none", 1: "k_scan", 2: "k_agg_lean", 3: "k_agg_sparse",
                      9: "k_count_reg",
                      11: "k_group_reg", 12: "k_group_sparse", 14: "k_agg_sparse over roaring containers",
                      15: "k_group_sparse over roaring containers",
-                     16: "k_scan, DISTINCTCOUNT bitsets in LDS", 17: "k_scan, DISTINCTCOUNT bitsets in HBM"}
+                     16: "k_scan, DISTINCTCOUNT bitsets in LDS", 17: "k_scan, DISTINCTCOUNT bitsets in HBM",
+                     18: "k_scan, PERCENTILE histograms in LDS", 19: "k_scan, PERCENTILE histograms in HBM"}
 
 
 @dataclass
@@ -80,10 +83,28 @@ class DistinctColumn:
 
 
 @dataclass
+class HistogramColumn:
+    """A PERCENTILE aggregation's result column: per row a histogram over the aggregation's result dictionary (the
+    reference's DoubleArrayList of matched values, PercentileAggregationFunction.java:77-94, counted per value), the
+    dictionary's values and the rows' final values as the library computed them (the rank on the device)."""
+    hist: np.ndarray    # uint32 [rows, D]: matched docs of value i
+    values: np.ndarray  # the D dictionary values ascending, in the column's stored type
+    finals: np.ndarray  # float64 [rows]
+
+    def __len__(self):
+        return len(self.finals)
+
+    def value_counts(self, row: int) -> ValueCounts:
+        """The row's values as doubles with their counts (getDoubleValuesSV converts before the list sees them)."""
+        return ValueCounts.of(self.values.astype(np.float64), self.hist[row])
+
+
+@dataclass
 class IntermediateResult:
     """Combined server-side result: columnar group keys and intermediate aggregation results."""
     key_columns: List[object]   # per group-by column: numpy array (numeric) or list of str
-    # per aggregation: int64 (COUNT), float64 (SUM/MIN/MAX), uint8[n, m] (HLL), DistinctColumn (DISTINCTCOUNT)
+    # per aggregation: int64 (COUNT), float64 (SUM/MIN/MAX), uint8[n, m] (HLL), DistinctColumn (DISTINCTCOUNT),
+    # HistogramColumn (PERCENTILE)
     agg_columns: List[object]
     num_groups: int
     functions: List[str]
@@ -107,6 +128,8 @@ class IntermediateResult:
                 conv.append(list(col))
             elif f == DISTINCTCOUNT:  # value sets: partial results of different calls merge by value
                 conv.append([col.value_set(i) for i in range(self.num_groups)])
+            elif f == PERCENTILE:  # value multisets: partial results of different calls merge by value
+                conv.append([col.value_counts(i) for i in range(self.num_groups)])
             else:
                 conv.append(col.tolist())
         for i in range(self.num_groups):
@@ -179,7 +202,9 @@ class _QueryStruct:
         aggs = (N.Aggregation * max(1, len(q.aggregations)))(
             *[N.Aggregation(_AGG[a.function], s(a.column) if a.column else None,
                             a.log2m if a.function == DISTINCTCOUNTHLL else 0,
-                            s(a.column2) if a.column2 else None, N.EXPR_CODES[a.op]) for a in q.aggregations])
+                            s(a.column2) if a.column2 else None, N.EXPR_CODES[a.op],
+                            float(a.percentile) if a.function == PERCENTILE else 0.0,
+                            int(a.name_form) if a.function == PERCENTILE else 0) for a in q.aggregations])
         self.keep += [node_arr, pred_arr, gb, aggs]
         end_ms = 0
         if "timeoutMs" in q.options:
@@ -416,6 +441,15 @@ class GpuContext:
                 counts = np.zeros(n, np.int32)
                 N.check(L.ph_result_distinct_counts(r, k, counts.ctypes.data))
                 arr = DistinctColumn(bits, values, counts)
+            elif a.function == PERCENTILE:
+                dt, es, cnt = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int64()
+                N.check(L.ph_result_percentile_dictionary(r, k, ctypes.byref(dt), ctypes.byref(es), ctypes.byref(cnt)))
+                d = cnt.value
+                hist = view(L.ph_result_aggregation_data(r, k), 4 * max(1, d) * n).view(np.uint32).reshape(n, max(1, d))
+                values = view(L.ph_result_percentile_values(r, k), d * es.value).view(_KEY_DTYPE[dt.value])
+                finals = np.zeros(n, np.float64)
+                N.check(L.ph_result_percentile_final(r, k, finals.ctypes.data))
+                arr = HistogramColumn(hist[:, :d], values, finals)
             elif a.function == COUNT:
                 arr = view(L.ph_result_aggregation_data(r, k), 8 * n).view(np.int64)
             else:

@@ -24,7 +24,8 @@ DATA_TYPES = {"INT": PH_INT, "LONG": PH_LONG, "FLOAT": PH_FLOAT, "DOUBLE": PH_DO
 
 PH_PRED_EQ, PH_PRED_NOT_EQ, PH_PRED_IN, PH_PRED_NOT_IN, PH_PRED_RANGE = range(5)
 PH_FILTER_AND, PH_FILTER_OR, PH_FILTER_NOT, PH_FILTER_PREDICATE = range(4)
-PH_AGG_COUNT, PH_AGG_SUM, PH_AGG_MIN, PH_AGG_MAX, PH_AGG_DISTINCTCOUNTHLL, PH_AGG_DISTINCTCOUNT = range(6)
+(PH_AGG_COUNT, PH_AGG_SUM, PH_AGG_MIN, PH_AGG_MAX, PH_AGG_DISTINCTCOUNTHLL, PH_AGG_DISTINCTCOUNT,
+ PH_AGG_PERCENTILE) = range(7)
 
 
 class PinotHipError(RuntimeError):
@@ -84,7 +85,9 @@ EXPR_CODES = {None: PH_EXPR_NONE, "*": PH_EXPR_MULT, "-": PH_EXPR_SUB, "+": PH_E
 
 class Aggregation(ctypes.Structure):
     _fields_ = [("type", ctypes.c_int32), ("column", ctypes.c_char_p), ("log2m", ctypes.c_int32),
-                ("column2", ctypes.c_char_p), ("expr_op", ctypes.c_int32)]
+                ("column2", ctypes.c_char_p), ("expr_op", ctypes.c_int32),
+                # PERCENTILE only (zero otherwise): 0..100, and 1 for the `PERCENTILEnn(col)` spelling's column name
+                ("percentile", ctypes.c_double), ("percentile_name_form", ctypes.c_int32)]
 
 
 class OrderBy(ctypes.Structure):
@@ -142,6 +145,7 @@ EXPORTED_SYMBOLS = (
     "ph_star_tree_check", "ph_star_tree_hll_pair_check",
     "ph_result_distinct_dictionary", "ph_result_distinct_values", "ph_result_distinct_words",
     "ph_result_distinct_counts",
+    "ph_result_percentile_dictionary", "ph_result_percentile_values", "ph_result_percentile_final",
 )
 
 _lib = None
@@ -209,6 +213,10 @@ def lib():
         "ph_result_distinct_values": ([vp, i32], vp),
         "ph_result_distinct_words": ([vp, i32], i32),
         "ph_result_distinct_counts": ([vp, i32, vp], ctypes.c_int),
+        "ph_result_percentile_dictionary": ([vp, i32, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i64)],
+                                            ctypes.c_int),
+        "ph_result_percentile_values": ([vp, i32], vp),
+        "ph_result_percentile_final": ([vp, i32, vp], ctypes.c_int),
         "ph_query_dense_layout": ([vp, ctypes.POINTER(Query), ctypes.POINTER(vp), i32, ctypes.POINTER(DenseLayout)],
                                   ctypes.c_int),
         "ph_query_execute_dense": ([vp, ctypes.POINTER(Query), ctypes.POINTER(vp), i32, ctypes.POINTER(vp),

@@ -27,7 +27,9 @@ UNBOUNDED = "*"
 # Aggregation function types supported on this path (AggregationFunctionFactory.java:186-263).
 COUNT, SUM, MIN, MAX, DISTINCTCOUNTHLL = "COUNT", "SUM", "MIN", "MAX", "DISTINCTCOUNTHLL"
 DISTINCTCOUNT = "DISTINCTCOUNT"  # exact: the size of the value set (DistinctCountAggregationFunction.java:61-68)
-SUPPORTED_AGGREGATIONS = (COUNT, SUM, MIN, MAX, DISTINCTCOUNTHLL, DISTINCTCOUNT)
+# exact: element (int)(n * p / 100) of the sorted matched values (PercentileAggregationFunction.java:146-158)
+PERCENTILE = "PERCENTILE"
+SUPPORTED_AGGREGATIONS = (COUNT, SUM, MIN, MAX, DISTINCTCOUNTHLL, DISTINCTCOUNT, PERCENTILE)
 DEFAULT_HLL_LOG2M = 8  # CommonConstants.Helix.DEFAULT_HYPERLOGLOG_LOG2M (CommonConstants.java:96-97)
 DEFAULT_NUM_GROUPS_LIMIT = 100_000  # InstancePlanMakerImplV2.DEFAULT_NUM_GROUPS_LIMIT (:72-73)
 DEFAULT_QUERY_LIMIT = 10
@@ -122,13 +124,38 @@ class FilterContext:
 EXPR_OPS = {"*": "times", "-": "minus", "+": "plus"}
 
 
+def java_double_string(v: float) -> str:
+    """Java's Double.toString of a percentile (0..100): shortest round-trip digits, at least one after the point
+    ("90.0", "99.9"), computerised scientific notation below 1e-3 ("1.0E-4")."""
+    v = float(v)
+    if v != 0.0 and abs(v) < 1e-3:
+        from decimal import Decimal
+        sign, digits, exp = Decimal(repr(v)).normalize().as_tuple()
+        rest = "".join(map(str, digits[1:])) or "0"
+        return f"{'-' if sign else ''}{digits[0]}.{rest}E{len(digits) + exp - 1}"
+    return repr(v)
+
+
+def parse_percentile(text: str, integer: bool) -> float:
+    """parsePercentileToInt / parsePercentileToDouble (AggregationFunctionFactory.java:376-386)."""
+    try:
+        p = float(int(text)) if integer else float(text)
+    except ValueError:
+        raise SqlParseError(f"Invalid percentile: {text}")
+    if not 0.0 <= p <= 100.0:  # (NaN fails the comparison too)
+        raise SqlParseError(f"Invalid percentile: {text}")
+    return p
+
+
 @dataclass(frozen=True)
 class AggregationSpec:
-    function: str           # COUNT | SUM | MIN | MAX | DISTINCTCOUNTHLL | DISTINCTCOUNT
+    function: str           # COUNT | SUM | MIN | MAX | DISTINCTCOUNTHLL | DISTINCTCOUNT | PERCENTILE
     column: Optional[str]   # None for COUNT(*); the first operand of an expression
     log2m: int = DEFAULT_HLL_LOG2M
     column2: Optional[str] = None  # second operand of `column <op> column2`
     op: Optional[str] = None       # "*", "-" or "+" (None: plain column)
+    percentile: float = 0.0        # PERCENTILE: 0..100
+    name_form: int = 0             # PERCENTILE: 1 for the `PERCENTILEnn(col)` spelling (the result column name only)
 
     def columns(self) -> List[str]:
         return [c for c in (self.column, self.column2) if c]
@@ -137,6 +164,10 @@ class AggregationSpec:
         arg = "*" if self.column is None else self.column
         if self.op:
             arg = f"{EXPR_OPS[self.op]}({self.column},{self.column2})"
+        if self.function == PERCENTILE:  # PercentileAggregationFunction.getResultColumnName (:60-64)
+            if self.name_form:
+                return f"percentile{int(self.percentile)}({arg})"
+            return f"percentile({arg}, {java_double_string(self.percentile)})"
         if self.function == DISTINCTCOUNTHLL and self.log2m != DEFAULT_HLL_LOG2M:
             arg = f"{arg},{self.log2m}"
         return f"{self.function.lower()}({arg})"
@@ -261,6 +292,19 @@ class _Parser:
 
     def agg_call(self) -> Optional[AggregationSpec]:
         t, n = self.peek(), self.peek(1)
+        pm = re.fullmatch(r"PERCENTILE(\d*)", t[1].upper()) if t[0] == "id" and n == ("op", "(") else None
+        if pm:  # PERCENTILE(col, p) | PERCENTILEnn(col)  (AggregationFunctionFactory.java:72-128)
+            self.i += 2
+            col = self.ident()
+            if pm.group(1):
+                if self.accept("op", ","):
+                    raise SqlParseError(f"{t[1]} takes one argument")
+                pct, form = parse_percentile(pm.group(1), True), 1
+            else:
+                self.expect("op", ",")
+                pct, form = parse_percentile(self.literal(), False), 0
+            self.expect("op", ")")
+            return AggregationSpec(PERCENTILE, col, DEFAULT_HLL_LOG2M, None, None, pct, form)
         if t[0] == "id" and n == ("op", "(") and t[1].upper() in SUPPORTED_AGGREGATIONS:
             fn = t[1].upper()
             self.i += 2

@@ -4,7 +4,8 @@ Mirrors the final steps the reference applies after the server-side combine:
 
 * ``AggregationFunction.extractFinalResult`` -- COUNT -> long, SUM/MIN/MAX -> double,
   DISTINCTCOUNTHLL -> ``HyperLogLog.cardinality()`` (DistinctCountHLLAggregationFunction.java:362-364),
-  DISTINCTCOUNT -> the value set's size as int (DistinctCountAggregationFunction.java:61-68).
+  DISTINCTCOUNT -> the value set's size as int (DistinctCountAggregationFunction.java:61-68),
+  PERCENTILE -> element (int)(n * p / 100) of the sorted values (PercentileAggregationFunction.java:146-158).
 * ``IndexedTable.finish`` / ``GroupByDataTableReducer.reduceAndSetResults`` -- ORDER BY over group-by
   columns and aggregations (ASC/DESC), then LIMIT (core/data/table/IndexedTable.java:148-173,
   core/query/reduce/GroupByDataTableReducer.java:99).
@@ -21,7 +22,7 @@ from typing import Any, List, Sequence
 
 import numpy as np
 
-from .query import COUNT, DISTINCTCOUNT, DISTINCTCOUNTHLL, MAX, MIN, SUM, QueryContext
+from .query import COUNT, DISTINCTCOUNT, DISTINCTCOUNTHLL, MAX, MIN, PERCENTILE, SUM, QueryContext
 
 
 def _java_round(x: float) -> int:
@@ -79,6 +80,58 @@ def set_serialize(values, data_type: str) -> bytes:
     return head + np.asarray(vals, dtype=dt).tobytes()
 
 
+@dataclass(frozen=True, eq=False)
+class ValueCounts:
+    """A PERCENTILE intermediate result: the reference's DoubleArrayList of matched values
+    (PercentileAggregationFunction.java:77-94) as a multiset -- the distinct doubles ascending and how often each
+    occurs.  Partial results of different calls have different dictionaries, so they merge by value."""
+    values: np.ndarray  # float64, ascending, distinct
+    counts: np.ndarray  # int64, the same length
+
+    @staticmethod
+    def of(values, counts=None) -> "ValueCounts":
+        v = np.asarray(values, dtype=np.float64).reshape(-1)
+        c = np.ones(len(v), np.int64) if counts is None else np.asarray(counts, dtype=np.int64).reshape(-1)
+        keep = c > 0
+        u, inv = np.unique(v[keep], return_inverse=True)
+        total = np.zeros(len(u), np.int64)
+        np.add.at(total, inv.reshape(-1), c[keep])
+        return ValueCounts(u, total)
+
+    def merge(self, other: "ValueCounts") -> "ValueCounts":  # DoubleArrayList.addAll
+        return ValueCounts.of(np.concatenate([self.values, other.values]), np.concatenate([self.counts, other.counts]))
+
+    @property
+    def size(self) -> int:
+        return int(self.counts.sum())
+
+    def sorted_values(self) -> np.ndarray:
+        return np.repeat(self.values, self.counts)
+
+    def __eq__(self, other):
+        return (isinstance(other, ValueCounts) and np.array_equal(self.values, other.values)
+                and np.array_equal(self.counts, other.counts))
+
+
+def percentile_final(vc: ValueCounts, percentile: float) -> float:
+    """PercentileAggregationFunction.extractFinalResult (:146-158): -inf for an empty list; the largest value for
+    p = 100; else the element of rank (int)((long) size * p / 100) -- double arithmetic, truncated -- in ascending
+    order (clamped to size - 1)."""
+    n = vc.size
+    if n == 0:
+        return float("-inf")
+    if percentile == 100:
+        return float(vc.values[-1])
+    rank = min(n - 1, max(0, int(float(n) * float(percentile) / 100.0)))
+    return float(vc.values[int(np.searchsorted(np.cumsum(vc.counts), rank, side="right"))])
+
+
+def double_list_serialize(vc: ValueCounts) -> bytes:
+    """ObjectSerDeUtils DoubleArrayList serializer (ObjectSerDeUtils.java:328-357): int32 BE size, then the doubles
+    BE.  Values are written ascending; the reference writes arrival order and sorts at the broker."""
+    return np.array([vc.size], dtype=">i4").tobytes() + vc.sorted_values().astype(">f8").tobytes()
+
+
 def merge_intermediate(function: str, a, b):
     """AggregationFunction.merge of two intermediate results of one group: COUNT / SUM add, MIN / MAX, HyperLogLog
     registers max, DISTINCTCOUNT value sets union (by value: the partial results' dictionaries may differ)."""
@@ -90,6 +143,8 @@ def merge_intermediate(function: str, a, b):
         return max(a, b)
     if function == DISTINCTCOUNT:
         return frozenset(a) | frozenset(b)
+    if function == PERCENTILE:
+        return a.merge(b)
     return np.maximum(a, b)  # HyperLogLog.addAll
 
 
@@ -109,6 +164,8 @@ def final_value(spec, value):
         return hll_cardinality(value, spec.log2m)
     if spec.function == DISTINCTCOUNT:
         return len(value)
+    if spec.function == PERCENTILE:
+        return percentile_final(value, spec.percentile)
     return float(value)
 
 
