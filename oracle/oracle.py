@@ -1067,6 +1067,16 @@ def execute(q, segments: Sequence[OracleSegment], num_threads: int = 1, filter_s
     if q.filter is None and not q.group_by and q.aggregations and all(
             a.function in ("COUNT", "MIN", "MAX", "DISTINCTCOUNTHLL") for a in q.aggregations):
         stats[2] = 0
+        # MIN / MAX are the dictionaries' first / last entries (NonScanBasedAggregationOperator.java:153-166), merged
+        # over the segments: a NaN, sorted last, is MAX's answer and never MIN's -- unlike the scan's Math.min fold
+        for j, a in enumerate(q.aggregations):
+            if a.function in ("MIN", "MAX") and not getattr(a, "op", None) and segments:
+                v = float("inf") if a.function == "MIN" else float("-inf")
+                for s in segments:
+                    d = s.columns[a.column].dictionary
+                    if s.num_docs and len(d):
+                        v = _math_min(v, float(d[0])) if a.function == "MIN" else _math_max(v, float(d[-1]))
+                merged[0][j] = v
     return OracleResult(keys, merged, OracleStats(*stats))
 
 
@@ -1199,6 +1209,19 @@ def _java_compare(a, b) -> int:
     return (a > b) - (a < b)
 
 
+def _math_min(a: float, b: float) -> float:
+    """Math.min (AggregationFunction.merge of MIN): a NaN operand gives NaN, -0.0 is below 0.0."""
+    if a != a or b != b:
+        return float("nan")
+    return b if _java_compare(float(b), float(a)) < 0 else a
+
+
+def _math_max(a: float, b: float) -> float:
+    if a != a or b != b:
+        return float("nan")
+    return b if _java_compare(float(b), float(a)) > 0 else a
+
+
 def _segment_trim(res, q, seg: OracleSegment, unions, nagg, size, hll_idx=(), log2m=8):
     """TableResizer.trimInSegmentResults (TableResizer.java:321-343, makeHeap / downHeap :233-262) over one segment's
     groups fed in ArrayBasedHolder order (ascending raw key over the segment's dictIds, column 0 least significant,
@@ -1319,8 +1342,8 @@ def _merge(res, q, merged_keys, merged, key_list, nagg, hll_idx, m, keep_rows=No
             if f in ("COUNT", "SUM"):
                 dst[j] = dst[j] + row[j]
             elif f == "MIN":
-                dst[j] = min(dst[j], row[j])
+                dst[j] = _math_min(dst[j], row[j])
             elif f == "MAX":
-                dst[j] = max(dst[j], row[j])
+                dst[j] = _math_max(dst[j], row[j])
             else:
                 dst[j] = np.maximum(dst[j], row[j])

@@ -365,6 +365,19 @@ static void seg_grow(seg_result* r, int nagg, int hll_bytes) {
   r->cap = nc;
 }
 
+/* Math.min / Math.max (MinAggregationFunction.java:89-118, MaxAggregationFunction.java:90-119): a NaN operand gives
+ * NaN, -0.0 is below 0.0 */
+static double java_math_min(double a, double b) {
+  if (a != a || b != b) return NAN;
+  if (a == 0.0 && b == 0.0) return signbit(a) ? a : b;
+  return b < a ? b : a;
+}
+static double java_math_max(double a, double b) {
+  if (a != a || b != b) return NAN;
+  if (a == 0.0 && b == 0.0) return signbit(a) ? b : a;
+  return b > a ? b : a;
+}
+
 static void agg_init(const or_query* q, double* a) {
   for (int k = 0; k < q->num_aggs; k++) {
     switch (q->agg_fn[k]) {
@@ -488,12 +501,12 @@ static void run_segment(const or_query* q, const or_segment* s, seg_result* r) {
           case OR_AGG_SUM: a[k] += agg_value(q, s, k, doc); break;
           case OR_AGG_MIN: {
             double v = agg_value(q, s, k, doc);
-            if (v < a[k]) a[k] = v;
+            a[k] = java_math_min(a[k], v);
             break;
           }
           case OR_AGG_MAX: {
             double v = agg_value(q, s, k, doc);
-            if (v > a[k]) a[k] = v;
+            a[k] = java_math_max(a[k], v);
             break;
           }
           case OR_AGG_HLL: {
@@ -574,8 +587,8 @@ static void merge_locked(combine_ctx* c, seg_result* r) {
       switch (q->agg_fn[k]) {
         case OR_AGG_COUNT:
         case OR_AGG_SUM: dst[k] += src[k]; break;
-        case OR_AGG_MIN: if (src[k] < dst[k]) dst[k] = src[k]; break;
-        case OR_AGG_MAX: if (src[k] > dst[k]) dst[k] = src[k]; break;
+        case OR_AGG_MIN: dst[k] = java_math_min(dst[k], src[k]); break;
+        case OR_AGG_MAX: dst[k] = java_math_max(dst[k], src[k]); break;
         default: break;
       }
     }

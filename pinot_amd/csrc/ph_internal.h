@@ -428,6 +428,20 @@ __host__ __device__ inline double double_from_order_key(int64_t k) {
   __builtin_memcpy(&d, &b, 8);
   return d;
 }
+// Math.min / Math.max keys (MinAggregationFunction.java:89-118, MaxAggregationFunction.java:90-119): any NaN wins, so
+// MIN sends every NaN below -Infinity's key and MAX above +Infinity's, whatever its sign bit; both ends decode to a
+// NaN through double_from_order_key.  `d` is the value `key` was made from (0.0 beside an integer term's value).
+__host__ __device__ inline int64_t min_order_key(int64_t key, double d) { return d != d ? INT64_MIN : key; }
+__host__ __device__ inline int64_t max_order_key(int64_t key, double d) { return d != d ? INT64_MAX : key; }
+// Math.min / Math.max of two doubles (host merges): NaN wins, -0.0 < 0.0
+inline double java_min(double a, double b) {
+  if (a != a || b != b) return __builtin_nan("");
+  return double_order_key(b) < double_order_key(a) ? b : a;
+}
+inline double java_max(double a, double b) {
+  if (a != a || b != b) return __builtin_nan("");
+  return double_order_key(b) > double_order_key(a) ? b : a;
+}
 
 // ------------------------------------------------------------------ device memory
 struct DeviceBuffer {

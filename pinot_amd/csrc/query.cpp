@@ -1524,7 +1524,7 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
           Column& c = *s->columns.at(a.column);
           if (c.cardinality == 0 || s->num_docs == 0) continue;
           double x = value_as_double(c.dict, a.type == PH_AGG_MIN ? 0 : c.cardinality - 1);
-          v = a.type == PH_AGG_MIN ? std::min(v, x) : std::max(v, x);
+          v = a.type == PH_AGG_MIN ? java_min(v, x) : java_max(v, x);  // AggregationFunction.merge of the segments
         }
         memcpy(res->aggs[k].data(), &v, 8);
       } else if (a.type == PH_AGG_DISTINCTCOUNT) {

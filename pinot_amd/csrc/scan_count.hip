@@ -235,8 +235,9 @@ __global__ void __launch_bounds__(kBlock) k_agg_sparse(const KParams p) {
       if (ops & OPS_SUM) {
         if (p.val_is_int[j]) isum[j] += iv; else dsum[j] += dv;
       }
-      if (ops & OPS_MIN) vmin[j] = iv < vmin[j] ? iv : vmin[j];
-      if (ops & OPS_MAX) vmax[j] = iv > vmax[j] ? iv : vmax[j];
+      const int64_t ivn = min_order_key(iv, dv), ivx = max_order_key(iv, dv);
+      if (ops & OPS_MIN) vmin[j] = ivn < vmin[j] ? ivn : vmin[j];
+      if (ops & OPS_MAX) vmax[j] = ivx > vmax[j] ? ivx : vmax[j];
     }
     for (int h = 0; h < p.num_hll && h < kMaxHll; ++h) {
       ColRef col = S->cols[p.hll_slot[h]];

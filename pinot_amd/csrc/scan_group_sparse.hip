@@ -255,8 +255,8 @@ __global__ void __launch_bounds__(kBlock) k_group_sparse(const KParams p) {
           if (is_int) atomicAdd(reinterpret_cast<unsigned long long*>(sb) + g, (unsigned long long)iv);
           else atomicAdd(reinterpret_cast<double*>(sb) + g, dv);
         }
-        if (ops & OPS_MIN) atomicMin(mnb + g, (long long)iv);
-        if (ops & OPS_MAX) atomicMax(mxb + g, (long long)iv);
+        if (ops & OPS_MIN) atomicMin(mnb + g, (long long)min_order_key(iv, dv));
+        if (ops & OPS_MAX) atomicMax(mxb + g, (long long)max_order_key(iv, dv));
       }
       // every lane has read its list entries before the next step rewrites the list
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");

@@ -830,8 +830,9 @@ __device__ __forceinline__ void process_tile(const KParams& p, SegPtr S, uint8_t
           if (ops & OPS_SUM) {
             if (p.val_is_int[j]) acc.isum[j] += iv; else acc.dsum[j] += vd[j];
           }
-          if (ops & OPS_MIN) acc.vmin[j] = iv < acc.vmin[j] ? iv : acc.vmin[j];
-          if (ops & OPS_MAX) acc.vmax[j] = iv > acc.vmax[j] ? iv : acc.vmax[j];
+          const int64_t ivn = min_order_key(iv, vd[j]), ivx = max_order_key(iv, vd[j]);
+          if (ops & OPS_MIN) acc.vmin[j] = ivn < acc.vmin[j] ? ivn : acc.vmin[j];
+          if (ops & OPS_MAX) acc.vmax[j] = ivx > acc.vmax[j] ? ivx : acc.vmax[j];
         } else {
           void* sb = local ? (void*)(smem + p.lds_sum_off[j]) : p.out_sum[j];
           long long* mnb = local ? reinterpret_cast<long long*>(smem + p.lds_min_off[j])
@@ -842,8 +843,8 @@ __device__ __forceinline__ void process_tile(const KParams& p, SegPtr S, uint8_t
             if (p.val_is_int[j]) atomicAdd(reinterpret_cast<unsigned long long*>(sb) + g, (unsigned long long)iv);
             else atomicAdd(reinterpret_cast<double*>(sb) + g, vd[j]);
           }
-          if (ops & OPS_MIN) atomicMin(mnb + g, (long long)iv);
-          if (ops & OPS_MAX) atomicMax(mxb + g, (long long)iv);
+          if (ops & OPS_MIN) atomicMin(mnb + g, (long long)min_order_key(iv, vd[j]));
+          if (ops & OPS_MAX) atomicMax(mxb + g, (long long)max_order_key(iv, vd[j]));
         }
       }
 #pragma unroll

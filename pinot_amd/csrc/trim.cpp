@@ -208,8 +208,8 @@ class ValueMerge {
         const int t = out_->agg_types[k];
         if (t == PH_AGG_COUNT) dst.c[k] += row.c[k];
         else if (t == PH_AGG_SUM) dst.d[k] += row.d[k];
-        else if (t == PH_AGG_MIN) dst.d[k] = std::min(dst.d[k], row.d[k]);
-        else if (t == PH_AGG_MAX) dst.d[k] = std::max(dst.d[k], row.d[k]);
+        else if (t == PH_AGG_MIN) dst.d[k] = java_min(dst.d[k], row.d[k]);
+        else if (t == PH_AGG_MAX) dst.d[k] = java_max(dst.d[k], row.d[k]);
         else
           for (size_t i = 0; i < dst.hll[k].size(); ++i) dst.hll[k][i] = std::max(dst.hll[k][i], row.hll[k][i]);
       }

@@ -17,6 +17,7 @@ returned in key order so results are deterministic.
 from __future__ import annotations
 
 import math
+import struct
 from dataclasses import dataclass
 from typing import Any, List, Sequence
 
@@ -132,15 +133,37 @@ def double_list_serialize(vc: ValueCounts) -> bytes:
     return np.array([vc.size], dtype=">i4").tobytes() + vc.sorted_values().astype(">f8").tobytes()
 
 
+def _double_compare_key(x) -> int:
+    """An int whose order is Double.compare's (NaN largest, -0.0 < 0.0)."""
+    x = float(x)
+    if x != x:
+        return 0x7FF8000000000000
+    b = struct.unpack("<q", struct.pack("<d", x))[0]
+    return b if b >= 0 else b ^ 0x7FFFFFFFFFFFFFFF
+
+
+def math_min(a, b) -> float:
+    """Java's Math.min: a NaN operand gives NaN, -0.0 is below 0.0 (Python's min keeps whichever came first)."""
+    if a != a or b != b:
+        return float("nan")
+    return b if _double_compare_key(b) < _double_compare_key(a) else a
+
+
+def math_max(a, b) -> float:
+    if a != a or b != b:
+        return float("nan")
+    return b if _double_compare_key(b) > _double_compare_key(a) else a
+
+
 def merge_intermediate(function: str, a, b):
     """AggregationFunction.merge of two intermediate results of one group: COUNT / SUM add, MIN / MAX, HyperLogLog
     registers max, DISTINCTCOUNT value sets union (by value: the partial results' dictionaries may differ)."""
     if function in (COUNT, SUM):
         return a + b
     if function == MIN:
-        return min(a, b)
+        return math_min(a, b)
     if function == MAX:
-        return max(a, b)
+        return math_max(a, b)
     if function == DISTINCTCOUNT:
         return frozenset(a) | frozenset(b)
     if function == PERCENTILE:
@@ -182,7 +205,9 @@ def reduce_groups(q: QueryContext, keys: Sequence[tuple], aggs: Sequence[Sequenc
                 c = q.group_by.index(ob.ref)
                 idx.sort(key=lambda i, c=c: keys[i][c], reverse=not ob.asc)
             else:
-                idx.sort(key=lambda i, k=ob.ref: finals[i][k], reverse=not ob.asc)
+                # Double.compare order: a NaN would make Python's comparison sort inconsistent
+                idx.sort(key=lambda i, k=ob.ref: (_double_compare_key(finals[i][k]) if isinstance(finals[i][k], float)
+                                                   else finals[i][k]), reverse=not ob.asc)
         idx = idx[: q.limit]
     rows = []
     for i in idx:

@@ -180,6 +180,19 @@ def test_hll_serialized_layout_against_reference_fixture():
     assert dec == regs.tolist()
 
 
+def test_min_max_of_negative_zero_and_nan_are_math_min_max():
+    # MIN / MAX fold Math.min / Math.max (a scanned NaN gives NaN, -0.0 < 0.0), in the scan and in the segments' merge;
+    # pinned against the plain reference of tests/float_ref.py (more cases: tests/test_float_aggs_cpu.py)
+    from tests import float_ref as R
+    vals = [np.array([-0.0, 2.0, np.nan]), np.array([0.0, 1.0])]
+    segs = [O.build_segment(f"mz{i}", {"d": (v, "DOUBLE"), "f": (np.arange(len(v), dtype=np.int32), "INT")})
+            for i, v in enumerate(vals)]
+    for where, kept in ((" WHERE f < 2", [v[:2] for v in vals]), (" WHERE f >= 0 AND f < 9", vals)):
+        r = O.execute(parse_sql(f"SELECT MIN(d), MAX(d) FROM t{where}"), segs)
+        assert R.same_double(r.aggs[0][0], R.java_min(np.concatenate(kept))), where  # -0.0 / NaN
+        assert R.same_double(r.aggs[0][1], R.java_max(np.concatenate(kept))), where  # 2.0 / NaN
+
+
 def test_segment_trim_heap_keeps_the_top_groups():
     # TableResizer's heap (oracle._segment_trim) keeps exactly the top `size` groups when the ORDER BY values are
     # distinct; a trimmed segment's dropped groups lose that segment's partial aggregates in the combine
