@@ -240,6 +240,8 @@ typedef struct {
   int64_t num_segments_matched;
   int32_t num_groups_limit_reached;
   int32_t sum_precision_flag;              /* 1 if an integer SUM reached 2^53 (double rounding differs) */
+                                           /* (a SUM that could pass 2^63 over the call's docs is added in double, not
+                                              int64; dense partials refuse it with PH_ERR_UNSUPPORTED instead) */
   double device_ms;                        /* kernel time of the query, HIP events */
   double host_ms;                          /* planning + result materialisation */
   int32_t plan_mode;                       /* physical plan: -2 index-only count (FastFilteredCount), -1

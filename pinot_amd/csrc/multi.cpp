@@ -271,6 +271,7 @@ ph_result* multi_execute(ph_ctx* x, const ph_query* q, ph_segment* const* segs, 
   auto dense = [&](int k, int op) {
     DenseArgs a{op, nullptr, 0, 0, nullptr};
     if (!have_tables) a.dicts = &dicts[k];
+    for (ph_segment* s : all) a.total_docs += s->num_docs;  // every device's: the bound of an integer SUM's int64 partials
     return a;
   };
   // a shape the dense tables do not serve: every device runs the query on its segments, the results merge on the
@@ -292,9 +293,14 @@ ph_result* multi_execute(ph_ctx* x, const ph_query* q, ph_segment* const* segs, 
   if (star_tree_serves_any(q, all.data(), (int32_t)all.size())) return host_merge();
   if (fresh) {
     try {
-      DenseArgs la = dense(active[0], DENSE_LAYOUT);
-      la.layout = &lay->layout;
-      query_execute_impl(x->devs[active[0]], q, by[active[0]].data(), (int32_t)by[active[0]].size(), &la);
+      // planned on every active device: a shape one of them refuses over its own segments (an integer SUM whose int64
+      // partials could wrap) merges by value on all of them
+      for (size_t a = 0; a < active.size(); ++a) {
+        ph_dense_layout other{};
+        DenseArgs la = dense(active[a], DENSE_LAYOUT);
+        la.layout = a == 0 ? &lay->layout : &other;
+        query_execute_impl(x->devs[active[a]], q, by[active[a]].data(), (int32_t)by[active[a]].size(), &la);
+      }
     } catch (const Error& e) {
       if (e.code != PH_ERR_UNSUPPORTED) throw;
       lay->layout.num_groups = -1;  // remembered: this shape merges by value

@@ -474,6 +474,9 @@ struct DenseArgs {
   // star-tree views in this call (startree.cpp): a view's filter is its traversal's documents AND the remaining
   // predicates, not the query's filter tree
   const std::map<const ph_segment*, struct StarSegPlan>* star = nullptr;
+  // dense ops: the docs of every segment whose partials are added into these tables, when the caller knows them (the
+  // in-library multi-device execute); 0 = unknown (the cross-rank API: other ranks' docs are not visible)
+  int64_t total_docs = 0;
 };
 // One star-tree view of a query (StarTreeFilterOperator.getFilterOperator, StarTreeFilterOperator.java:157-199): the
 // star-tree documents the traversal matched (sorted, disjoint, inclusive (start, end) pairs), the remaining predicate

@@ -1350,6 +1350,9 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
   }
   // |value| bound of term j over the queried segments (integer terms only; 0 when unknown)
   std::vector<double> term_amax(nvals, 0.0);
+  std::vector<int> val_widened(nvals, 0);  // an integer term summed in double: its int64 sum over the docs could wrap
+  double docs_queried = 0.0;
+  for (auto* s : segs) docs_queried += (double)s->num_docs;
   for (int j = 0; j < nvals; ++j) {
     int is_int = 1;
     double amax[2] = {0.0, 0.0};
@@ -1387,6 +1390,21 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
     // an integer expression is exact in int64 only while it cannot overflow; else double arithmetic, as the
     // reference computes it
     if (val_exprs[j] && bound >= 4.0e18) is_int = 0;
+    // an integer SUM is exact in int64 only while |term| x docs stays below 2^63; past that the term is summed in
+    // double, the reference's own arithmetic (SumAggregationFunction adds (double) value).  Dense partials are int64
+    // tables that other ranks add into: the multi-device execute passes the docs of every device and gets the same
+    // bound; a cross-rank call sees only its own docs, so it serves terms that cannot wrap over 2^32 docs (every INT
+    // column) and refuses the rest
+    if (is_int && (val_ops[j] & 1)) {
+      if (dop) {
+        const bool wraps = dn->total_docs > 0 ? bound * std::max(docs_queried, (double)dn->total_docs) >= 9.0e18
+                                              : bound * std::max(docs_queried, 4294967296.0) > 9223372036854775808.0;
+        if (wraps) fail(PH_ERR_UNSUPPORTED, "dense partials of an integer SUM that could pass 2^63");
+      } else if (bound * docs_queried >= 9.0e18) {
+        is_int = 0;
+        val_widened[j] = 1;
+      }
+    }
     val_is_int[j] = is_int;
     term_amax[j] = is_int ? bound : 0.0;
   }
@@ -2085,7 +2103,7 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
       off = (hb < 1e12 && off < SIZE_MAX / 4) ? off + (size_t)hb : SIZE_MAX / 2;
     }
     const bool part_ok = num_hll == 0 && ntab == 0 && nvals <= 1 && (nvals == 0 || (val_is_int[0] && !val_exprs[0] && vmax >= vmin &&
-                                                                       (uint64_t)(vmax - vmin) < (1ull << 32))) &&
+                                                                       ((uint64_t)vmax - (uint64_t)vmin) < (1ull << 32))) &&
                          G <= ((int64_t)kPartMaxParts << kPartKeysLog2) && !any_limit &&
                          !ctx->has(OPT_DISABLE_PARTITION);
     // LDS-private tables up to 64 KiB; r2 measured 96 KiB tables (one workgroup per CU) slower than the HBM table
@@ -2581,6 +2599,7 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
     for (int k = 0; d.fkind == FK_CONJ && k < d.nconj; ++k) g |= d.cset[k] != nullptr || d.clen[k] == 0;
     for (int gi = 0; gi < q->num_group_by; ++gi) g |= d.cols[kp.group_slot[gi]].remap != nullptr;
     for (int j = 0; j < nvals; ++j) g |= d.vals[j].kind != VK_PACKED || (val_exprs[j] && d.vals2[j].kind != VK_PACKED);
+    for (int j = 0; j < nvals; ++j) g |= val_widened[j] && !val_exprs[j];  // widened after the read (k_scan's LATE forms)
     if (g && mode != MODE_COUNT) kp.late_prefetch = 1;
     if (g && mode == MODE_COUNT && d.fkind != FK_RANGE && d.fkind != FK_ALL && d.fkind != FK_DOCRANGE) kp.late_prefetch = 1;
   }
@@ -2655,7 +2674,7 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
   kp.lds_fast = mode == MODE_GROUP_LDS && num_hll == 0 && ntab == 0 && nvals <= 1 && !kp.late_prefetch &&
                 !ctx->has(OPT_LDS_GENERIC);
   if (nvals == 1)
-    kp.lds_fast = kp.lds_fast && val_is_int[0] && !val_exprs[0] && vmax >= vmin && (uint64_t)(vmax - vmin) < (1ull << 32);
+    kp.lds_fast = kp.lds_fast && val_is_int[0] && !val_exprs[0] && vmax >= vmin && ((uint64_t)vmax - (uint64_t)vmin) < (1ull << 32);
   for (auto& d : dsegs)
     if ((d.fkind != FK_ALL && d.fkind != FK_RANGE && d.fkind != FK_DOCRANGE) ||
         (nvals == 1 && d.vals[0].kind != VK_PACKED))
@@ -2737,7 +2756,7 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
       // docs (bounded by its workgroup's) keep count < 2^24 and the offset sum < 2^40
       int32_t mcw = 1;
       for (auto& ch : chunks) mcw = std::max(mcw, ch.word_end - ch.word_begin);
-      const uint64_t vrange = nvals ? (uint64_t)(vmax - vmin) : 0;
+      const uint64_t vrange = nvals ? ((uint64_t)vmax - (uint64_t)vmin) : 0;
       auto layout = [&](bool pack) {
         kp.lds_copy_bytes = (int32_t)(((size_t)G * (pack ? 16 : 20) + 15) / 16 * 16);
         kp.lds_copies = (size_t)kWaves * kp.lds_copy_bytes <= 48 * 1024 ? kWaves : 1;
@@ -3219,7 +3238,7 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
       while (klo > 8 && (G >> (klo - 1)) < 256) --klo;  // small key spaces: more partitions, more workgroups
       const int64_t P = (G + (int64_t(1) << klo) - 1) >> klo;
       if (P > kPartMaxParts) fail(PH_ERR_UNSUPPORTED, "partitioned group-by too large");
-      const int vbits = nvals ? std::max(1, bits_for_range((uint64_t)(vmax - vmin))) : 0;
+      const int vbits = nvals ? std::max(1, bits_for_range(((uint64_t)vmax - (uint64_t)vmin))) : 0;
       rec64 = (klo + vbits > 32) ? 1 : 0;
       int64_t batch_rows = int64_t(1) << 31;  // one batch: launch tails of many short batches cost more than MALL reuse saves
       if (ctx->has(OPT_PART_BATCH_ROWS)) batch_rows = std::max<int64_t>(1 << 16, ctx->opt(OPT_PART_BATCH_ROWS));
@@ -3701,6 +3720,7 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
         if (raw >= (int64_t(1) << 53) || raw <= -(int64_t(1) << 53)) stats.sum_precision_flag = 1;
       } else {
         memcpy(&v, &raw, 8);
+        if (val_widened[j] && std::fabs(v) >= 9007199254740992.0) stats.sum_precision_flag = 1;
       }
     } else if (cnt_for_default == 0) {
       v = t == PH_AGG_MIN ? INFINITY : -INFINITY;  // Min/MaxAggregationFunction defaults
@@ -3888,7 +3908,7 @@ ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const
     // a finalised key shard has no scan: its matched docs are the sum of its group counts (k_compact_count)
     if (fin) stats.num_docs_scanned = docs;
     for (int k = 0; k < nagg; ++k) {
-      if (q->aggregations[k].type != PH_AGG_SUM || !val_is_int[agg_val[k]]) continue;
+      if (q->aggregations[k].type != PH_AGG_SUM || (!val_is_int[agg_val[k]] && !val_widened[agg_val[k]])) continue;
       if (!fin && sum_bounded[agg_val[k]]) continue;
       const double* sv = reinterpret_cast<const double*>(res->aggs[k].data());
       for (int64_t r = 0; r < R; ++r)

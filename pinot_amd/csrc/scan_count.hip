@@ -230,6 +230,9 @@ __global__ void __launch_bounds__(kBlock) k_agg_sparse(const KParams p) {
           dv = EX == PH_EXPR_MULT ? (1.0 * x) * y : (EX == PH_EXPR_SUB ? x - y : x + y);
           iv = double_order_key(dv);
         }
+      } else if (!p.val_is_int[j] && vc.kind != VK_DICT_F64) {  // an integer column summed in double
+        dv = (double)iv;
+        iv = double_order_key(dv);
       }
       const int ops = p.val_ops[j];
       if (ops & OPS_SUM) {

@@ -224,6 +224,9 @@ __global__ void __launch_bounds__(kBlock) k_group_sparse(const KParams p) {
               dv = EX == PH_EXPR_MULT ? (1.0 * x) * y : (EX == PH_EXPR_SUB ? x - y : x + y);
               iv = double_order_key(dv);
             }
+          } else if (!is_int && vc.kind != VK_DICT_F64) {  // an integer column summed in double
+            dv = (double)iv;
+            iv = double_order_key(dv);
           }
         }
         // the workgroup's slot: the key itself (LDS table) or its group-cache slot (probe <= 8), else HBM

@@ -735,6 +735,10 @@ __device__ __forceinline__ void process_tile(const KParams& p, SegPtr S, uint8_t
               vd[j] = eop == PH_EXPR_MULT ? (1.0 * x) * y : (eop == PH_EXPR_SUB ? x - y : x + y);
               vi[j] = double_order_key(vd[j]);
             }
+          } else if (LATE && !p.val_is_int[j] && vkind[j] != VK_DICT_F64) {
+            // an integer column summed in double (its int64 sum could wrap): (double) value, as the reference adds it
+            vd[j] = (double)vi[j];
+            vi[j] = double_order_key(vd[j]);
           }
         }
 #pragma unroll

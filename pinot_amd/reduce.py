@@ -158,8 +158,12 @@ def math_max(a, b) -> float:
 def merge_intermediate(function: str, a, b):
     """AggregationFunction.merge of two intermediate results of one group: COUNT / SUM add, MIN / MAX, HyperLogLog
     registers max, DISTINCTCOUNT value sets union (by value: the partial results' dictionaries may differ)."""
-    if function in (COUNT, SUM):
-        return a + b
+    if function == COUNT:
+        return int(a) + int(b)
+    if function == SUM:
+        # the intermediate result of SUM is a double (SumAggregationFunction.merge); an integer-typed partial (numpy
+        # int64) would wrap where the doubles do not: 3 x 2^62 + 2^62 is 2^64, not 0
+        return float(a) + float(b)
     if function == MIN:
         return math_min(a, b)
     if function == MAX:
