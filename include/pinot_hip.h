@@ -191,7 +191,37 @@ typedef struct {
   double percentile;            /* PERCENTILE: 0..100; 0 for every other type */
   int32_t percentile_name_form; /* PERCENTILE: 0 = `percentile(col, 90.0)`, 1 = `percentile90(col)`: the result column
                                    name only (PercentileAggregationFunction.java:60-64); 0 for every other type */
+  int32_t filter;               /* 0: unfiltered; else 1 + the index in ph_query.filter_nodes of the root of this
+                                   aggregation's FILTER(WHERE ...) tree (see "Filtered aggregations" below) */
 } ph_aggregation;
+
+/* Filtered aggregations: `agg(...) FILTER(WHERE <filter>)` for COUNT / SUM / MIN / MAX over a plain column (and
+ * COUNT(*)), with or without a WHERE clause and a GROUP BY, the reference's FilteredAggregationOperator /
+ * FilteredGroupByOperator over AggregationFunctionUtils.buildFilteredAggregateProjectOperators
+ * (AggregationFunctionUtils.java:191-267).  A sub-filter's nodes and predicates live in the query's filter_nodes /
+ * predicates arrays and are planned exactly as a WHERE clause is (an unknown column or an unparsable literal is
+ * PH_ERR_BAD_QUERY); structurally equal trees (FilterContext.equals: type, children in order, predicate) share one
+ * pipeline whatever their node indices.  A bad index, or a tree whose nodes form a cycle, is PH_ERR_INVALID_ARGUMENT.
+ * Sub-filter f aggregates over docs(WHERE) AND docs(f), the unfiltered functions over docs(WHERE).  A group is a
+ * result row when any pipeline saw a doc of it; a function whose pipeline saw none of the group holds its result
+ * holder's default (COUNT 0, SUM 0.0, MIN +Infinity, MAX -Infinity).  The statistics are the sums over the pipelines
+ * (FilteredGroupByOperator.java:149-151); SUM keeps the integer contract of sum_precision_flag.
+ * ph_exec_stats.scan_kernel is PH_KERNEL_SCAN_FILTERED; plan_mode 1 / 2 / 3 as the tables live in registers, LDS
+ * or HBM.  Never answered from a star-tree (the TODO at FilteredGroupByOperator.java:108), from metadata or by the
+ * index-only count.  Shapes that return PH_ERR_UNSUPPORTED, each with its own message (the CPU plan serves them):
+ *   - a FILTER on DISTINCTCOUNTHLL, DISTINCTCOUNT or PERCENTILE, or any of them beside a filtered aggregation;
+ *   - a FILTER on a 2-operand expression, or such an expression beside a filtered aggregation;
+ *   - multi-device contexts and the dense-partial entry points;
+ *   - segment group trim (min_segment_group_trim_size > 0 with ORDER BY);
+ *   - a call in which a segment could reach num_groups_limit (min(product of the group-by cardinalities, docs) >=
+ *     the limit): the reference's group ids then depend on the order of a HashMap over FilterContexts;
+ *   - key spaces beyond the dense group tables (8 bytes x (pipelines + value slots) per key over the 32 GB budget,
+ *     or 2^40 keys);
+ *   - more than 8 distinct sub-filters, or more than 4 distinct aggregated columns;
+ *   - under a WHERE clause that neither matches all nor is empty on a segment: a sub-filter of several predicates, or
+ *     one over a legacy (version 1) range index -- the statistic of the reference's CombinedFilterOperator is derived
+ *     for single-leaf sub-filters only.
+ * ph_filter_execute ignores aggregation filters, as it ignores aggregations. */
 
 typedef struct {
   int32_t num_filter_nodes;
@@ -286,8 +316,10 @@ enum {
                                        (plan_mode 1 otherwise, plan_mode 3) */
   PH_KERNEL_SCAN_HIST_LDS = 18,     /* k_scan<MODE, ..., LATE = 4>: PERCENTILE histograms (and any DISTINCTCOUNT bitsets
                                        of the query) in the workgroup's LDS, flushed at the end (plan_mode 1 or 2) */
-  PH_KERNEL_SCAN_HIST_HBM = 19      /* k_scan<MODE, ..., LATE = 4>: PERCENTILE counters added straight into the HBM
+  PH_KERNEL_SCAN_HIST_HBM = 19,     /* k_scan<MODE, ..., LATE = 4>: PERCENTILE counters added straight into the HBM
                                        table, equal (row, id) lanes of a wave combined first (plan_mode 1 or 3) */
+  PH_KERNEL_SCAN_FILTERED = 20      /* k_scan_filtered<MODE>: filtered aggregations, every pipeline's doc bitmap applied
+                                       in one pass over the group-by and value columns (plan_mode 1, 2 or 3) */
 };
 
 /* ------------------------------------------------------------------ context */

@@ -146,7 +146,10 @@ public class GpuCombinePlanNode extends CombinePlanNode {
       ByteBuffer[] aggs = new ByteBuffer[functions.length];
       GpuResultSchema.RowObjects[] distinct = new GpuResultSchema.RowObjects[functions.length];
       for (int k = 0; k < functions.length; k++) {
-        names[nk + k] = functions[k].getResultColumnName();
+        names[nk + k] = _queryContext.hasFilteredAggregations()
+            ? org.apache.pinot.core.query.aggregation.function.AggregationFunctionUtils.getResultColumnName(functions[k],
+                _queryContext.getFilteredAggregationFunctions().get(k).getRight())
+            : functions[k].getResultColumnName();
         types[nk + k] = functions[k].getIntermediateResultColumnType();
         aggs[k] = aggColumn(res, k, functions[k]);
         distinct[k] = GpuResultSchema.rowObjects(res, k, functions[k]);  // once per aggregation, not per row (else null)

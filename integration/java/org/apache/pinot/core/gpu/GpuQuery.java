@@ -24,7 +24,7 @@ import org.apache.pinot.segment.spi.AggregationFunctionType;
 /**
  * QueryContext -> the ph_query descriptor of PinotHipJni.queryExecute (the Java twin of pinot_amd/query.py +
  * engine._QueryStruct).  Returns null for shapes outside the GPU path, so the plan maker keeps the CPU plan:
- * filtered aggregations, star-tree, null handling, non-identifier group-by expressions, aggregations other than
+ * null handling, non-identifier group-by expressions, aggregations other than
  * COUNT / SUM / MIN / MAX / DISTINCTCOUNTHLL / DISTINCTCOUNT / PERCENTILE (over a column; SUM / MIN / MAX also over a 2-operand
  * mult/sub/add), predicates other than
  * EQ / NOT_EQ / IN / NOT_IN / RANGE on identifiers, and a segment group trim (GroupByOperator.java:114-130) ordered
@@ -44,7 +44,7 @@ public final class GpuQuery {
   }
 
   public static GpuQuery compile(QueryContext ctx) {
-    if (!QueryContextUtils.isAggregationQuery(ctx) || ctx.isNullHandlingEnabled() || ctx.hasFilteredAggregations()) {
+    if (!QueryContextUtils.isAggregationQuery(ctx) || ctx.isNullHandlingEnabled()) {
       return null;
     }
     Builder b = new Builder();
@@ -59,13 +59,21 @@ public final class GpuQuery {
           groupBy.add(e.getIdentifier());
         }
       }
+      // each aggregation's descriptor ends with its filter: 0, or 1 + the root of its FILTER(WHERE ...) tree in the
+      // node list (ph_aggregation.filter).  Every filtered function packs its own tree; the library finds the
+      // structurally equal ones itself (FilterContext.equals).  The shapes it does not serve come back as
+      // PH_ERR_UNSUPPORTED and the plan maker keeps the CPU plan.
       List<int[]> aggs = new ArrayList<>();
-      for (AggregationFunction f : ctx.getAggregationFunctions()) {
-        int[] a = b.aggregation(f);
+      AggregationFunction[] functions = ctx.getAggregationFunctions();
+      for (int i = 0; i < functions.length; i++) {
+        int[] a = b.aggregation(functions[i]);
         if (a == null) {
           return null;
         }
-        aggs.add(a);
+        FilterContext filter = ctx.hasFilteredAggregations() ? ctx.getFilteredAggregationFunctions().get(i).getRight() : null;
+        int[] withFilter = java.util.Arrays.copyOf(a, a.length + 1);
+        withFilter[a.length] = filter == null ? 0 : b.filter(filter) + 1;
+        aggs.add(withFilter);
       }
       // [numFilterNodes, filterRoot, numPredicates, numGroupBy, numAggregations, nodes..., predicates...,
       //  group-by..., aggregations...]
@@ -104,6 +112,16 @@ public final class GpuQuery {
           int gi = ctx.getGroupByExpressions().indexOf(e);
           Integer ai = e.getType() == ExpressionContext.Type.FUNCTION
               ? ctx.getAggregationFunctionIndexMap().get(e.getFunction()) : null;
+          // an ORDER BY on a filtered aggregation is the function filter(agg, condition): it resolves through the
+          // (function, filter) index map, as QueryContext's builder registers it
+          if (ai == null && gi < 0 && e.getType() == ExpressionContext.Type.FUNCTION && ctx.hasFilteredAggregations()
+              && "filter".equalsIgnoreCase(e.getFunction().getFunctionName()) && e.getFunction().getArguments().size() == 2
+              && e.getFunction().getArguments().get(0).getType() == ExpressionContext.Type.FUNCTION) {
+            FilterContext obFilter = org.apache.pinot.common.request.context.RequestContextUtils.getFilter(
+                e.getFunction().getArguments().get(1));
+            ai = ctx.getFilteredAggregationsIndexMap().get(org.apache.commons.lang3.tuple.Pair.of(
+                e.getFunction().getArguments().get(0).getFunction(), obFilter));
+          }
           if (gi >= 0) {
             order.add(new int[]{0, gi, ob.isAsc() ? 1 : 0});
           } else if (ai != null) {

@@ -176,7 +176,12 @@ final class GpuResultSchema {
       types[g] = keyType(PinotHipJni.resultKeyType(res, g));
     }
     for (int k = 0; k < functions.length; k++) {
-      names[nk + k] = functions[k].getResultColumnName();
+      // a filtered function's column carries its FilterContext (AggregationFunctionUtils.getResultColumnName :269-275),
+      // the name ph_result_datatable writes too
+      names[nk + k] = ctx.hasFilteredAggregations()
+          ? org.apache.pinot.core.query.aggregation.function.AggregationFunctionUtils.getResultColumnName(functions[k],
+              ctx.getFilteredAggregationFunctions().get(k).getRight())
+          : functions[k].getResultColumnName();
       types[nk + k] = functions[k].getIntermediateResultColumnType();
     }
     return new DataSchema(names, types);

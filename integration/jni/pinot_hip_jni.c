@@ -233,6 +233,7 @@ static int decode_query(const jint* desc, jsize nd, const char** strs, jsize ns,
       memcpy(&b->aggs[i].percentile, &bits, sizeof bits);
     }
     NEXT(b->aggs[i].percentile_name_form);
+    NEXT(b->aggs[i].filter); /* 0, or 1 + the root of the FILTER(WHERE ...) tree in the node list */
   }
   if (k < nd) { /* optional trailing block: ORDER BY + LIMIT + minSegmentGroupTrimSize [+ skipStarTree] */
     NEXT(q->num_order_by);

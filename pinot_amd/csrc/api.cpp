@@ -346,6 +346,12 @@ int ph_query_execute(ph_ctx* ctx, const ph_query* query, ph_segment* const* segm
       if (query->min_segment_group_trim_size > 0 && query->num_group_by > 0 && query->num_order_by > 0)
         fail(PH_ERR_UNSUPPORTED, std::string(fn) + " with segment group trim (minSegmentGroupTrimSize)");
     }
+    if (has_filtered_aggregation(query)) {  // their own plan (filtered.cpp): one pass, a doc bitmap per pipeline
+      filtered_validate(query);
+      if (ctx->devs.size() > 1) fail(PH_ERR_UNSUPPORTED, "filtered aggregations on a multi-device context");
+      *out = filtered_execute(&ctx->c, query, segments, num_segments);
+      return;
+    }
     if (ctx->devs.size() > 1)
       *out = multi_execute(ctx, query, segments, num_segments);  // per device, merged in the library
     else if (query && query->min_segment_group_trim_size > 0 && query->num_group_by > 0 && query->num_order_by > 0)
@@ -430,6 +436,10 @@ static Context* dense_device(ph_ctx* ctx, ph_segment* const* segs, int32_t n) {
 }
 
 static void reject_dense_shapes(const ph_query* q) {
+  if (has_filtered_aggregation(q)) {
+    filtered_validate(q);
+    fail(PH_ERR_UNSUPPORTED, "filtered aggregations on dense partials");
+  }
   if (const char* fn = row_table_function(q)) fail(PH_ERR_UNSUPPORTED, std::string(fn) + " on dense partials");
   if (q && q->min_segment_group_trim_size > 0 && q->num_group_by > 0 && q->num_order_by > 0)
     fail(PH_ERR_UNSUPPORTED, "segment group trim (minSegmentGroupTrimSize) on dense partials");
@@ -438,8 +448,10 @@ static void reject_dense_shapes(const ph_query* q) {
 int ph_query_dense_layout(ph_ctx* ctx, const ph_query* query, ph_segment* const* segments, int32_t num_segments,
                           ph_dense_layout* out) {
   return guarded([&] {
-    if (!ctx || !out) fail(PH_ERR_INVALID_ARGUMENT, "null argument");
+    // the query's shape is judged first, from the descriptor alone: a refused shape needs no context (host-only callers
+    // and the CPU tests ask with a null one)
     reject_dense_shapes(query);
+    if (!ctx || !out) fail(PH_ERR_INVALID_ARGUMENT, "null argument");
     DenseArgs d{DENSE_LAYOUT, nullptr, 0, 0, out};
     query_execute_impl(dense_device(ctx, segments, num_segments), query, segments, num_segments, &d);
   });

@@ -175,6 +175,9 @@ std::vector<uint8_t> result_to_datatable(const ph_result* r, const ph_query* q, 
   }
   for (int k = 0; k < na; ++k) {
     names.push_back(agg_column_name(q->aggregations[k]));
+    // AggregationFunctionUtils.getResultColumnName (:269-275): a filtered function's name carries its FilterContext
+    if (q->aggregations[k].filter)
+      names.back() += " FILTER(WHERE " + filter_to_string(q, q->aggregations[k].filter - 1) + ")";
     const int t = r->agg_types[k];
     types.push_back(t == PH_AGG_COUNT ? "LONG" : ((t == PH_AGG_DISTINCTCOUNTHLL || t == PH_AGG_DISTINCTCOUNT || t == PH_AGG_PERCENTILE) ? "OBJECT" : "DOUBLE"));
     width[nk + k] = 8;

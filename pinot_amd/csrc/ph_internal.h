@@ -391,6 +391,53 @@ struct PctFinishParams {
   double agg_p[kMaxAggs];         // its percentile, 0..100
 };
 
+// Filtered aggregations (scan_filtered.hip, filtered.cpp): k_scan_filtered's launch.  A pipeline is a doc set the
+// reference builds a projection for (AggregationFunctionUtils.java:191-267): pipeline 0 the unfiltered functions' (the
+// main filter), pipeline i >= 1 main AND distinct sub-filter i.  A slot is one SUM / MIN / MAX of one value term over one
+// pipeline; COUNT(*) reads its pipeline's doc counts.
+constexpr int kFMaxSubFilters = 8;                // distinct FILTER(WHERE ...) clauses of one query
+constexpr int kFMaxPipes = kFMaxSubFilters + 1;
+constexpr int kFMaxSlots = kMaxAggs;
+constexpr int kFMaxVals = kMaxVals;               // distinct value columns
+enum : int32_t {
+  FOP_SUM_I = 0,    // int64 add
+  FOP_SUM_F = 1,    // float64 add
+  FOP_SUM_I2F = 2,  // an integer term added in float64 (its int64 sum over the call's docs could pass 2^63)
+  FOP_MIN_I = 3,
+  FOP_MAX_I = 4,
+  FOP_MIN_F = 5,    // NaN-aware order keys (min_order_key / max_order_key)
+  FOP_MAX_F = 6,
+};
+struct FSegment {
+  int32_t num_docs;
+  uint32_t empty;                                 // bit p: pipeline p sees no doc of this segment
+  // pipeline p's docs: ma[p] AND mb[p], 64-bit doc-bitmap words (bit i of word w = doc 64 w + i); nullptr = every doc
+  const unsigned long long* ma[kFMaxPipes];
+  const unsigned long long* mb[kFMaxPipes];
+  const uint32_t* gfwd[kMaxGroupCols];            // group-by column g: packed dictIds, their width, dictId -> key id
+  const int32_t* gremap[kMaxGroupCols];           //   (nullptr: identity)
+  int32_t gbits[kMaxGroupCols];
+  const uint32_t* vfwd[kFMaxVals];                // value column v: packed dictIds and the 8-byte dictionary table
+  const void* vtable[kFMaxVals];                  //   (int64 for INT / LONG, float64 for FLOAT / DOUBLE)
+  int32_t vbits[kFMaxVals];
+};
+struct FParams {
+  const FSegment* segs;
+  const Chunk* chunks;
+  int32_t chunk_begin, chunk_end;
+  int32_t num_pipes, num_slots, num_vals, num_group_cols;
+  int64_t group_stride[kMaxGroupCols];
+  int64_t num_groups;                             // dense key space (1 without a group-by)
+  int32_t slot_pipe[kFMaxSlots];
+  int32_t slot_op[kFMaxSlots];                    // FOP_*
+  int32_t slot_val[kFMaxSlots];
+  long long* slot_out[kFMaxSlots];                // [num_groups] 8-byte cells, initialised to the op's identity
+  unsigned long long* pcount;                     // [num_pipes][num_groups] docs per pipeline and group (group-by)
+  unsigned long long* seg_count;                  // [segments][kFMaxPipes] docs per segment and pipeline
+};
+size_t filtered_lds_bytes(const FParams& p, int mode);
+void launch_scan_filtered(const FParams& p, int mode, int grid, hipStream_t s);
+
 // Kernel B of the partitioned group-by: aggregates one batch of records per partition in LDS, then merges
 // the partition's key range into the dense result table (each key range has exactly one owner block).
 struct PartAggParams {
@@ -992,6 +1039,19 @@ void star_tree_forget(Context& c, ph_segment* seg);  // api.cpp: drop a view's r
 // answered by FastFilteredCountOperator (COUNT(*) over an index-countable filter, AggregationPlanNode.java:183-188)
 std::vector<char> predicate_dict_ids(const ph_predicate& p, const Column& c, bool* always_true, bool* always_false);
 bool filter_index_countable(const ph_query* q, ph_segment* seg);
+// how the filter tree rooted at node `root` of q->filter_nodes plans on a segment: the planner's isResultEmpty /
+// isResultMatchingAll decisions, else whether the tree is one predicate whose leaf operator scans (a
+// ScanBasedFilterOperator) or answers from an index (sorted, inverted, exact range index), else a composite
+enum : int32_t { FP_EMPTY = 0, FP_ALL = 1, FP_SCAN_LEAF = 2, FP_INDEX_LEAF = 3, FP_COMPOSITE = 4 };
+int32_t filter_plan_class(const ph_query* q, int32_t root, ph_segment* seg);
+// filtered aggregations (filtered.cpp): ph_aggregation.filter != 0 somewhere in the query
+bool has_filtered_aggregation(const ph_query* q);
+void filtered_validate(const ph_query* q);  // host-only argument and shape checks of a filtered query
+ph_result* filtered_execute(Context* ctx, const ph_query* q, ph_segment* const* segs, int32_t nseg);
+// FilterContext.toString of the tree rooted at `root` (FilterContext.java:94-114 and each Predicate.toString)
+std::string filter_to_string(const ph_query* q, int32_t root);
+ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const* segs, int32_t nseg,
+                              const DenseArgs* dense);
 
 }  // namespace ph
 

@@ -1139,8 +1139,30 @@ bool filter_index_countable(const ph_query* q, ph_segment* seg) {
   return index_count(root, pl.bitmaps, seg->num_docs) >= 0;
 }
 
+int32_t filter_plan_class(const ph_query* q, int32_t root_index, ph_segment* seg) {
+  Planner pl;
+  pl.q = q;
+  std::vector<std::string> names;
+  for (int i = 0; i < q->num_predicates; ++i)
+    if (q->predicates[i].column && !pl.slot.count(q->predicates[i].column)) {
+      pl.slot[q->predicates[i].column] = (int)names.size();
+      names.push_back(q->predicates[i].column);
+    }
+  PNode root = pl.build(seg, root_index, 0);
+  const bool one_predicate = q->filter_nodes[root_index].type == PH_FILTER_PREDICATE;
+  const bool legacy = root.legacy_range;  // its boundary ranges are scanned: neither closed form holds
+  merge_same_column_leaves(root, [&](int slot) { return (int64_t)seg->columns.at(names[(size_t)slot])->cardinality; },
+                           &pl.bitmaps);
+  if (root.kind == L_NONE || seg->num_docs == 0) return FP_EMPTY;
+  if (root.kind == L_ALL) return FP_ALL;
+  if (!one_predicate || legacy) return FP_COMPOSITE;
+  return index_based(root) ? FP_INDEX_LEAF : FP_SCAN_LEAF;
+}
+
 ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const* segs_in, int32_t nseg,
                               const DenseArgs* dn) {
+  // filtered aggregations have their own plan (filtered.cpp); no other entry point scans them
+  if (has_filtered_aggregation(q)) fail(PH_ERR_UNSUPPORTED, "filtered aggregations on this entry point");
   const int dop = dn ? dn->op : 0;
   const bool fin = dop == DENSE_FINALIZE;
   // ph_filter_execute: a COUNT(*) (no group-by) whose MODE_COUNT scan also writes every segment's doc bitmap

@@ -59,7 +59,8 @@ SCAN_KERNEL_NAMES = {0: "none", 1: "k_scan", 2: "k_agg_lean", 3: "k_agg_sparse",
                      11: "k_group_reg", 12: "k_group_sparse", 14: "k_agg_sparse over roaring containers",
                      15: "k_group_sparse over roaring containers",
                      16: "k_scan, DISTINCTCOUNT bitsets in LDS", 17: "k_scan, DISTINCTCOUNT bitsets in HBM",
-                     18: "k_scan, PERCENTILE histograms in LDS", 19: "k_scan, PERCENTILE histograms in HBM"}
+                     18: "k_scan, PERCENTILE histograms in LDS", 19: "k_scan, PERCENTILE histograms in HBM",
+                     20: "k_scan_filtered"}
 
 
 @dataclass
@@ -196,16 +197,21 @@ class _QueryStruct:
             return len(nodes) - 1
 
         root = add(q.filter) if q.filter is not None else -1
+        # every FILTER(WHERE ...) tree goes into the same node / predicate arrays under its own root; the library
+        # finds structurally equal trees itself (ph_aggregation.filter = 1 + root index, 0 = unfiltered)
+        agg_filter = [add(a.filter) + 1 if a.filter is not None else 0 for a in q.aggregations]
         node_arr = (N.FilterNode * max(1, len(nodes)))(*nodes)
         pred_arr = (N.Predicate * max(1, len(preds)))(*preds)
         gb = (ctypes.c_char_p * max(1, len(q.group_by)))(*[s(g) for g in q.group_by])
-        aggs = (N.Aggregation * max(1, len(q.aggregations)))(
-            *[N.Aggregation(_AGG[a.function], s(a.column) if a.column else None,
-                            a.log2m if a.function == DISTINCTCOUNTHLL else 0,
-                            s(a.column2) if a.column2 else None, N.EXPR_CODES[a.op],
-                            float(a.percentile) if a.function == PERCENTILE else 0.0,
-                            int(a.name_form) if a.function == PERCENTILE else 0) for a in q.aggregations])
-        self.keep += [node_arr, pred_arr, gb, aggs]
+        agg_arr = (N.FilteredAggregation * max(1, len(q.aggregations)))(
+            *[N.FilteredAggregation(_AGG[a.function], s(a.column) if a.column else None,
+                                    a.log2m if a.function == DISTINCTCOUNTHLL else 0,
+                                    s(a.column2) if a.column2 else None, N.EXPR_CODES[a.op],
+                                    float(a.percentile) if a.function == PERCENTILE else 0.0,
+                                    int(a.name_form) if a.function == PERCENTILE else 0, f)
+              for a, f in zip(q.aggregations, agg_filter)])
+        aggs = ctypes.cast(agg_arr, ctypes.POINTER(N.Aggregation))
+        self.keep += [node_arr, pred_arr, gb, agg_arr]
         end_ms = 0
         if "timeoutMs" in q.options:
             import time

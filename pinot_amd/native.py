@@ -90,6 +90,16 @@ class Aggregation(ctypes.Structure):
                 ("percentile", ctypes.c_double), ("percentile_name_form", ctypes.c_int32)]
 
 
+class FilteredAggregation(ctypes.Structure):
+    """ph_aggregation with its last field, ``filter`` (0: unfiltered, else 1 + the root's index in filter_nodes): an
+    int32 at offset 52, where ``Aggregation`` ends in tail padding.  Both layouts are the header's 56 bytes, and a
+    zero-initialised ``Aggregation`` is an unfiltered one; queries are packed with this struct."""
+    _fields_ = Aggregation._fields_ + [("filter", ctypes.c_int32)]
+
+
+PH_KERNEL_SCAN_FILTERED = 20
+
+
 class OrderBy(ctypes.Structure):
     _fields_ = [("kind", ctypes.c_int32), ("index", ctypes.c_int32), ("asc", ctypes.c_int32)]
 

@@ -45,10 +45,14 @@ class Predicate:
         return self.TYPE  # type: ignore[attr-defined]
 
 
+# Each predicate's to_string() is the reference's toString (the text of a filtered aggregation's result column name).
 @dataclass(frozen=True)
 class EqPredicate(Predicate):
     value: str
     TYPE = "EQ"
+
+    def to_string(self) -> str:  # EqPredicate.java:64-66
+        return f"{self.column} = '{self.value}'"
 
 
 @dataclass(frozen=True)
@@ -56,17 +60,26 @@ class NotEqPredicate(Predicate):
     value: str
     TYPE = "NOT_EQ"
 
+    def to_string(self) -> str:  # NotEqPredicate.java:63-65
+        return f"{self.column} != '{self.value}'"
+
 
 @dataclass(frozen=True)
 class InPredicate(Predicate):
     values: Tuple[str, ...]
     TYPE = "IN"
 
+    def to_string(self) -> str:  # InPredicate.java:58-66
+        return f"{self.column} IN (" + ",".join(f"'{v}'" for v in self.values) + ")"
+
 
 @dataclass(frozen=True)
 class NotInPredicate(Predicate):
     values: Tuple[str, ...]
     TYPE = "NOT_IN"
+
+    def to_string(self) -> str:  # NotInPredicate.java:58-66
+        return f"{self.column} NOT IN (" + ",".join(f"'{v}'" for v in self.values) + ")"
 
 
 @dataclass(frozen=True)
@@ -76,6 +89,17 @@ class RangePredicate(Predicate):
     lower_inclusive: bool = False
     upper_inclusive: bool = False
     TYPE = "RANGE"
+
+    def to_string(self) -> str:  # RangePredicate.java:122-134
+        c = self.column
+        if self.lower == UNBOUNDED:
+            return f"{c} {'<=' if self.upper_inclusive else '<'} '{self.upper}'"
+        if self.upper == UNBOUNDED:
+            return f"{c} {'>=' if self.lower_inclusive else '>'} '{self.lower}'"
+        if self.lower_inclusive and self.upper_inclusive:
+            return f"{c} BETWEEN '{self.lower}' AND '{self.upper}'"
+        return (f"({c} {'>=' if self.lower_inclusive else '>'} '{self.lower}' AND "
+                f"{c} {'<=' if self.upper_inclusive else '<'} '{self.upper}')")
 
 
 # --------------------------------------------------------------------------- filter tree
@@ -103,6 +127,14 @@ class FilterContext:
     @staticmethod
     def not_(c: "FilterContext") -> "FilterContext":
         return FilterContext("NOT", (c,))
+
+    def to_string(self) -> str:
+        """FilterContext.toString (FilterContext.java:94-114)."""
+        if self.type == "PREDICATE":
+            return self.predicate.to_string()
+        if self.type == "NOT":
+            return f"(NOT {self.children[0].to_string()})"
+        return "(" + f" {self.type} ".join(c.to_string() for c in self.children) + ")"
 
     def columns(self) -> List[str]:
         if self.type == "PREDICATE":
@@ -156,11 +188,17 @@ class AggregationSpec:
     op: Optional[str] = None       # "*", "-" or "+" (None: plain column)
     percentile: float = 0.0        # PERCENTILE: 0..100
     name_form: int = 0             # PERCENTILE: 1 for the `PERCENTILEnn(col)` spelling (the result column name only)
+    # agg(...) FILTER(WHERE <filter>): the function aggregates the docs of WHERE AND <filter>
+    # (AggregationFunctionUtils.buildFilteredAggregateProjectOperators, AggregationFunctionUtils.java:191-267)
+    filter: Optional[FilterContext] = None
 
     def columns(self) -> List[str]:
         return [c for c in (self.column, self.column2) if c]
 
     def result_name(self) -> str:
+        if self.filter is not None:  # AggregationFunctionUtils.getResultColumnName (:269-275)
+            from dataclasses import replace
+            return f"{replace(self, filter=None).result_name()} FILTER(WHERE {self.filter.to_string()})"
         arg = "*" if self.column is None else self.column
         if self.op:
             arg = f"{EXPR_OPS[self.op]}({self.column},{self.column2})"
@@ -291,6 +329,18 @@ class _Parser:
         return t[1]
 
     def agg_call(self) -> Optional[AggregationSpec]:
+        """An aggregation call with its optional `FILTER(WHERE <filter_expr>)` clause."""
+        agg = self.plain_agg_call()
+        t = self.peek()
+        if agg is not None and t[0] == "id" and t[1].upper() == "FILTER" and self.peek(1) == ("op", "("):
+            from dataclasses import replace
+            self.i += 2
+            self.expect("kw", "WHERE")
+            agg = replace(agg, filter=self.filter_expr())
+            self.expect("op", ")")
+        return agg
+
+    def plain_agg_call(self) -> Optional[AggregationSpec]:
         t, n = self.peek(), self.peek(1)
         pm = re.fullmatch(r"PERCENTILE(\d*)", t[1].upper()) if t[0] == "id" and n == ("op", "(") else None
         if pm:  # PERCENTILE(col, p) | PERCENTILEnn(col)  (AggregationFunctionFactory.java:72-128)
@@ -416,6 +466,9 @@ def parse_sql(sql: str) -> QueryContext:
         else:
             item = SelectItem("column", p.ident())
         if p.accept("kw", "AS"):
+            item.alias = p.ident()
+        elif agg is not None and agg.filter is not None and p.peek()[0] == "id":
+            # `SUM(c) FILTER(WHERE ...) sum1`: the alias without AS, after a FILTER clause only
             item.alias = p.ident()
         q.select.append(item)
         if not p.accept("op", ","):
