@@ -165,7 +165,42 @@ typedef struct {
  * tables beyond the dense table budget (4 bytes per value: the device table plus the host copy of the rows that can be
  * non-empty), key spaces beyond the dense group tables, more than 4 distinct PERCENTILE columns, and a call whose
  * segments hold 2^32 docs or more (the counters are uint32; a planner check only).  Never answered from a star-tree or
- * from metadata: with no filter and no group-by the reference scans too (plan_mode 1). */
+ * from metadata: with no filter and no group-by the reference scans too (plan_mode 1).
+ *
+ * PH_AGG_VARPOP / PH_AGG_VARSAMP / PH_AGG_STDDEVPOP / PH_AGG_STDDEVSAMP: the reference's VarianceAggregationFunction over
+ * a pinned single-value INT, LONG, FLOAT or DOUBLE column (a raw column too).  The intermediate result of a row is the
+ * reference's VarianceTuple of the row's `count` matched docs (VarianceTuple.java:25-33): 24 bytes in host order,
+ * {int64 count; double sum; double m2} with sum = sum(x) and m2 = sum((x - mean)^2); a row with no doc holds
+ * (0, 0.0, 0.0), which only an aggregation-only query that matched nothing returns.  The four functions over one
+ * column return the same tuple and differ in the final result (VarianceAggregationFunction.java:228-248: m2 / count or
+ * m2 / (count - 1), its square root for STDDEV, -Infinity for count 0 and for a sample function with count 1) and in
+ * the result column name.  The reference updates the tuple per doc (Chan's update, :80-121); here the scan adds the
+ * exact moments n, sum(d) and sum(d^2) of d = x - K, K a shift of the call taken from the first and last dictionary
+ * entries of the column in the queried segments:
+ *   - a column stored as INT or LONG: K = lo + (hi - lo) / 2 and dmax = max(hi - K, K - lo); with N the docs of the
+ *     call's segments the sums are exact integers while dmax N < 2^63 and dmax^2 N < 2^127 (every INT column; a LONG
+ *     column whose range is below about 2^47 at 2^32 docs): sum(d^2) in one 64-bit cell when dmax^2 N < 2^64, in 128
+ *     bits otherwise.  Then sum is the integer n K + sum(d) rounded once to double, and m2 is the exact integer
+ *     n sum(d^2) - sum(d)^2 rounded once to double and divided by (double) n: two roundings (2^-52 relative), exactly
+ *     0.0 when all values are equal, independent of the order of the docs and bit-reproducible;
+ *   - FLOAT / DOUBLE columns, and integer columns past those bounds: K is the midpoint as a double, the two sums are
+ *     added in double (order-dependent, as a DOUBLE SUM: within 1e-9 relative of sum|x| and of sum((x - K)^2)), and
+ *     sum = n K + sum(d), m2 = max(0, sum(d^2) - sum(d)^2 / n).
+ * Served: queries whose aggregations are all of this family or COUNT(*), with or without a WHERE clause and a GROUP BY,
+ * any number of such aggregations over at most 4 distinct columns.  log2m, column2 and percentile are ignored.
+ * ph_exec_stats.scan_kernel is PH_KERNEL_SCAN_MOMENTS; plan_mode 1 / 2 / 3.  num_docs_scanned is the matched docs,
+ * num_entries_scanned_in_filter the WHERE clause's ordinary statistic, num_entries_scanned_post_filter the matched docs
+ * x (group-by columns + distinct argument columns).  Never answered from a star-tree or from metadata.  Shapes that
+ * return PH_ERR_UNSUPPORTED, each with its own message (the CPU plan serves them):
+ *   - a STRING column, a sketch column or a non-NONE expr_op;
+ *   - SUM / MIN / MAX / DISTINCTCOUNTHLL / DISTINCTCOUNT / PERCENTILE beside a function of the family;
+ *   - a FILTER clause on or beside one;
+ *   - multi-device contexts and the dense-partial entry points;
+ *   - segment group trim (min_segment_group_trim_size > 0 with ORDER BY);
+ *   - a call in which a segment could reach num_groups_limit (min(product of the group-by cardinalities, docs) >= the
+ *     limit);
+ *   - key spaces beyond 2^40 keys or the dense table budget (8 + 48 bytes x distinct columns per key over 32 GB);
+ *   - more than 4 distinct argument columns. */
 typedef enum {
   PH_AGG_COUNT = 0,
   PH_AGG_SUM = 1,
@@ -173,7 +208,11 @@ typedef enum {
   PH_AGG_MAX = 3,
   PH_AGG_DISTINCTCOUNTHLL = 4,
   PH_AGG_DISTINCTCOUNT = 5,
-  PH_AGG_PERCENTILE = 6
+  PH_AGG_PERCENTILE = 6,
+  PH_AGG_VARPOP = 7,
+  PH_AGG_VARSAMP = 8,
+  PH_AGG_STDDEVPOP = 9,
+  PH_AGG_STDDEVSAMP = 10
 } ph_aggregation_type;
 
 /* 2-operand expression argument of SUM / MIN / MAX: `column <op> column2`, evaluated per row like the reference's
@@ -318,8 +357,10 @@ enum {
                                        of the query) in the workgroup's LDS, flushed at the end (plan_mode 1 or 2) */
   PH_KERNEL_SCAN_HIST_HBM = 19,     /* k_scan<MODE, ..., LATE = 4>: PERCENTILE counters added straight into the HBM
                                        table, equal (row, id) lanes of a wave combined first (plan_mode 1 or 3) */
-  PH_KERNEL_SCAN_FILTERED = 20      /* k_scan_filtered<MODE>: filtered aggregations, every pipeline's doc bitmap applied
+  PH_KERNEL_SCAN_FILTERED = 20,     /* k_scan_filtered<MODE>: filtered aggregations, every pipeline's doc bitmap applied
                                        in one pass over the group-by and value columns (plan_mode 1, 2 or 3) */
+  PH_KERNEL_SCAN_MOMENTS = 21       /* k_scan_moments<MODE, FORM> + k_moments_finish: the variance family as exact shifted
+                                       moments (plan_mode 1, 2 or 3 as the tables live in registers, LDS or HBM) */
 };
 
 /* ------------------------------------------------------------------ context */
@@ -472,7 +513,8 @@ const void* ph_result_key_data(const ph_result* r, int32_t group_by_index);
  * DISTINCTCOUNT uint32[W] bitset over the aggregation's result dictionary, W = ceil(D / 32): bit i & 31 of word
  * i >> 5 set means value i of the dictionary is present; bits past D are zero,
  * PERCENTILE uint32[D] histogram over the aggregation's result dictionary: the matched docs of each value
- * (PERCENTILE aggregations over one column return the same histogram) */
+ * (PERCENTILE aggregations over one column return the same histogram),
+ * VARPOP / VARSAMP / STDDEVPOP / STDDEVSAMP {int64 count; double sum; double m2}, 24 bytes (see PH_AGG_VARPOP) */
 int ph_result_aggregation(const ph_result* r, int32_t aggregation_index, void* out);
 const void* ph_result_aggregation_data(const ph_result* r, int32_t aggregation_index);
 /* DISTINCTCOUNT aggregation k.  Its result dictionary is the table dictionary of the column (ph_table_set_dictionary)

@@ -54,7 +54,33 @@ final class GpuResultSchema {
     if (f.getType() == AggregationFunctionType.PERCENTILE) {
       return new HistogramColumn(res, k);
     }
-    return null;
+    switch (f.getType()) {
+      case VARPOP:
+      case VARSAMP:
+      case STDDEVPOP:
+      case STDDEVSAMP:
+        return new VarianceColumn(res, k);
+      default:
+        return null;
+    }
+  }
+
+  /** VAR_POP / VAR_SAMP / STDDEV_POP / STDDEV_SAMP aggregation {@code k} of a result: 24-byte rows in host order,
+   *  {long count; double sum; double m2} -- the VarianceTuple the function's intermediate column (OBJECT,
+   *  VarianceAggregationFunction.java:217-220) holds. */
+  static final class VarianceColumn implements RowObjects {
+    private final ByteBuffer _rows;
+
+    VarianceColumn(long res, int k) {
+      _rows = PinotHipJni.resultAggregationBuffer(res, k, 24).order(ByteOrder.nativeOrder());
+    }
+
+    @Override
+    public Object row(int row) {
+      int at = 24 * row;
+      return new org.apache.pinot.segment.local.customobject.VarianceTuple(_rows.getLong(at), _rows.getDouble(at + 8),
+          _rows.getDouble(at + 16));
+    }
   }
 
   /** PERCENTILE aggregation {@code k} of a result (ph_result_percentile_*): uint32[D] histogram rows over the D values

@@ -127,8 +127,11 @@ std::string java_double_string(double v) {
 }
 
 std::string agg_column_name(const ph_aggregation& a) {
-  static const char* fn[] = {"count", "sum", "min", "max", "distinctcounthll", "distinctcount", "percentile"};
-  if (a.type < 0 || a.type > PH_AGG_PERCENTILE) fail(PH_ERR_INVALID_ARGUMENT, "unknown aggregation");
+  // (the variance family: getType().getName().toLowerCase(), BaseSingleInputAggregationFunction.java:43-45 over
+  // AggregationFunctionType.java:174-181)
+  static const char* fn[] = {"count", "sum", "min", "max", "distinctcounthll", "distinctcount", "percentile",
+                             "varpop", "varsamp", "stddevpop", "stddevsamp"};
+  if (a.type < 0 || a.type > PH_AGG_STDDEVSAMP) fail(PH_ERR_INVALID_ARGUMENT, "unknown aggregation");
   if (a.type == PH_AGG_COUNT) return "count(*)";
   if (a.type == PH_AGG_PERCENTILE) {  // PercentileAggregationFunction.getResultColumnName (:60-64)
     const std::string col = a.column ? a.column : "";
@@ -179,7 +182,7 @@ std::vector<uint8_t> result_to_datatable(const ph_result* r, const ph_query* q, 
     if (q->aggregations[k].filter)
       names.back() += " FILTER(WHERE " + filter_to_string(q, q->aggregations[k].filter - 1) + ")";
     const int t = r->agg_types[k];
-    types.push_back(t == PH_AGG_COUNT ? "LONG" : ((t == PH_AGG_DISTINCTCOUNTHLL || t == PH_AGG_DISTINCTCOUNT || t == PH_AGG_PERCENTILE) ? "OBJECT" : "DOUBLE"));
+    types.push_back(t == PH_AGG_COUNT ? "LONG" : ((t == PH_AGG_DISTINCTCOUNTHLL || t == PH_AGG_DISTINCTCOUNT || t == PH_AGG_PERCENTILE || t >= PH_AGG_VARPOP) ? "OBJECT" : "DOUBLE"));
     width[nk + k] = 8;
   }
   for (int c = 0; c < ncol; ++c) {
@@ -234,6 +237,15 @@ std::vector<uint8_t> result_to_datatable(const ph_result* r, const ph_query* q, 
         std::vector<uint32_t> w(words, 0);
         for (int j = 0; j < m; ++j) w[j / 6] |= (uint32_t)(reg[j] & 0x1f) << (5 * (j % 6));
         for (uint32_t x : w) var.i32((int32_t)x);
+      } else if (t >= PH_AGG_VARPOP && t <= PH_AGG_STDDEVSAMP) {
+        // VarianceTuple.toBytes (VarianceTuple.java:69-75) as ObjectType.VarianceTuple (ObjectSerDeUtils.java:137): long
+        // count, double sum, double m2, big-endian
+        uint64_t f[3];
+        memcpy(f, base + (size_t)g * 24, 24);
+        put_be(dst, (uint32_t)var.b.size(), 4);
+        put_be(dst + 4, 24u, 4);
+        var.i32(33);
+        for (uint64_t x : f) var.i64((int64_t)x);
       } else if (t == PH_AGG_PERCENTILE) {
         // the DoubleArrayList of the matched values (ObjectSerDeUtils.java:328-357): int objectType 3, int size, the
         // doubles -- each value of the row's histogram `count` times, ascending.  The reference writes arrival order

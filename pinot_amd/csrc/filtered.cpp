@@ -79,45 +79,6 @@ bool same_filter(const ph_query* q, int32_t a, int32_t b) {
   return true;
 }
 
-// per-call device buffers from the context's scratch pool, returned once the call's stream has drained
-struct Scratch {
-  Context* ctx;
-  hipStream_t st;
-  std::vector<std::unique_ptr<DeviceBuffer>> bufs;
-  Scratch(Context* c, hipStream_t s) : ctx(c), st(s) {}
-  ~Scratch() {
-    (void)hipStreamSynchronize(st);
-    for (auto& b : bufs) ctx->scratch_release(std::move(b));
-  }
-  template <class T>
-  T* alloc(size_t count) {
-    auto b = ctx->scratch_acquire(std::max<size_t>(16, sizeof(T) * count));
-    T* p = b->as<T>();
-    bufs.push_back(std::move(b));
-    return p;
-  }
-};
-
-void put_key(const Dictionary& d, int64_t id, uint8_t* dst, int32_t entry) {
-  switch (d.type) {
-    case PH_INT: { int32_t v = (int32_t)d.ints[(size_t)id]; memcpy(dst, &v, 4); break; }
-    case PH_LONG: memcpy(dst, &d.ints[(size_t)id], 8); break;
-    case PH_FLOAT: { float v = (float)d.reals[(size_t)id]; memcpy(dst, &v, 4); break; }
-    case PH_DOUBLE: memcpy(dst, &d.reals[(size_t)id], 8); break;
-    default:
-      memset(dst, 0, (size_t)entry);
-      memcpy(dst, d.strings[(size_t)id].data(), std::min<size_t>((size_t)entry, d.strings[(size_t)id].size()));
-  }
-}
-
-int32_t entry_size_of(const Dictionary& d) {
-  switch (d.type) {
-    case PH_INT: case PH_FLOAT: return 4;
-    case PH_LONG: case PH_DOUBLE: return 8;
-    default: return std::max(1, d.max_string_len);
-  }
-}
-
 }  // namespace
 
 bool has_filtered_aggregation(const ph_query* q) {

@@ -16,6 +16,7 @@
 #include <atomic>
 #include <exception>
 #include <cstdint>
+#include <cstring>
 #include <deque>
 #include <functional>
 #include <map>
@@ -438,6 +439,62 @@ struct FParams {
 size_t filtered_lds_bytes(const FParams& p, int mode);
 void launch_scan_filtered(const FParams& p, int mode, int grid, hipStream_t s);
 
+// Variance moments (scan_moments.hip, moments.cpp): VAR_POP / VAR_SAMP / STDDEV_POP / STDDEV_SAMP.  A slot is one
+// argument column; per group it accumulates S1 = sum(d) and S2 = sum(d^2) of d = value - K (K: the call's shift for the
+// column), beside the docs n of the group, which every slot shares.  A slot's form is chosen by the planner:
+constexpr int kMMaxSlots = 4;  // distinct argument columns of one query
+enum : int32_t {
+  MFORM_NARROW = 0,  // integer d, S2 in one u64 cell (dmax^2 x docs < 2^64: never carries)
+  MFORM_WIDE = 1,    // integer d, S2 in a (lo, hi) pair of u64 cells (a carry out of lo goes into hi)
+  MFORM_REAL = 2,    // d, S1 and S2 are doubles
+};
+struct MSegment {
+  int32_t num_docs;
+  const unsigned long long* mask;                 // the WHERE clause's doc bitmap (bit i of word w = doc 64 w + i);
+                                                  //   nullptr = every doc
+  const uint32_t* gfwd[kMaxGroupCols];            // group-by column g: packed dictIds, their width, dictId -> key id
+  const int32_t* gremap[kMaxGroupCols];           //   (nullptr: identity)
+  int32_t gbits[kMaxGroupCols];
+  const uint32_t* vfwd[kMMaxSlots];               // slot v: packed dictIds, their width and d_of[dictId]: int64
+  const long long* d_of[kMMaxSlots];              //   value - K, or the bits of the double (double)value - K
+  int32_t vbits[kMMaxSlots];
+};
+struct MParams {
+  const MSegment* segs;
+  const Chunk* chunks;
+  int32_t chunk_begin, chunk_end;
+  int32_t num_slots, num_group_cols;
+  int32_t slot_col[kMMaxSlots];                   // the MSegment column (vfwd / d_of index) of this launch's slot s
+  int64_t group_stride[kMaxGroupCols];
+  int64_t num_groups;                             // dense key space (1 without a group-by)
+  // zeroed [num_groups] tables; n and seg_count (docs per segment) are nullptr in a call's second and third launch
+  // (the slots of another form over the same docs), which then counts nothing
+  unsigned long long* n;
+  unsigned long long* s1[kMMaxSlots];
+  unsigned long long* s2lo[kMMaxSlots];
+  unsigned long long* s2hi[kMMaxSlots];           // MFORM_WIDE only
+  unsigned long long* seg_count;
+};
+// k_moments_finish: one thread per (group, slot) turns (n, S1, S2) into the reference's VarianceTuple
+struct MTuple {
+  int64_t count;
+  double sum, m2;
+};
+struct MFinishParams {
+  int64_t num_groups;
+  int32_t num_slots;
+  int32_t form[kMMaxSlots];
+  int64_t shift[kMMaxSlots];                      // K: an int64, or a double's bits (MFORM_REAL)
+  const unsigned long long* n;
+  const unsigned long long* s1[kMMaxSlots];
+  const unsigned long long* s2lo[kMMaxSlots];
+  const unsigned long long* s2hi[kMMaxSlots];
+  MTuple* out[kMMaxSlots];                        // [num_groups]
+};
+size_t moments_lds_bytes(const MParams& p, int mode, int form);
+void launch_scan_moments(const MParams& p, int mode, int form, int grid, hipStream_t s);
+void launch_moments_finish(const MFinishParams& p, hipStream_t s);
+
 // Kernel B of the partitioned group-by: aggregates one batch of records per partition in LDS, then merges
 // the partition's key range into the dense result table (each key range has exactly one owner block).
 struct PartAggParams {
@@ -854,6 +911,45 @@ struct LaneGuard {
   LaneGuard& operator=(const LaneGuard&) = delete;
 };
 
+// per-call device buffers from the context's scratch pool, returned once the call's stream has drained
+struct Scratch {
+  Context* ctx;
+  hipStream_t st;
+  std::vector<std::unique_ptr<DeviceBuffer>> bufs;
+  Scratch(Context* c, hipStream_t s) : ctx(c), st(s) {}
+  ~Scratch() {
+    (void)hipStreamSynchronize(st);
+    for (auto& b : bufs) ctx->scratch_release(std::move(b));
+  }
+  template <class T>
+  T* alloc(size_t count) {
+    auto b = ctx->scratch_acquire(std::max<size_t>(16, sizeof(T) * count));
+    T* p = b->as<T>();
+    bufs.push_back(std::move(b));
+    return p;
+  }
+};
+
+inline void put_key(const Dictionary& d, int64_t id, uint8_t* dst, int32_t entry) {
+  switch (d.type) {
+    case PH_INT: { int32_t v = (int32_t)d.ints[(size_t)id]; memcpy(dst, &v, 4); break; }
+    case PH_LONG: memcpy(dst, &d.ints[(size_t)id], 8); break;
+    case PH_FLOAT: { float v = (float)d.reals[(size_t)id]; memcpy(dst, &v, 4); break; }
+    case PH_DOUBLE: memcpy(dst, &d.reals[(size_t)id], 8); break;
+    default:
+      memset(dst, 0, (size_t)entry);
+      memcpy(dst, d.strings[(size_t)id].data(), std::min<size_t>((size_t)entry, d.strings[(size_t)id].size()));
+  }
+}
+
+inline int32_t entry_size_of(const Dictionary& d) {
+  switch (d.type) {
+    case PH_INT: case PH_FLOAT: return 4;
+    case PH_LONG: case PH_DOUBLE: return 8;
+    default: return std::max(1, d.max_string_len);
+  }
+}
+
 // kernels.hip
 void launch_scan(const KParams& p, int mode, int ngroup, int rec64, int grid, size_t lds, hipStream_t s);
 void launch_part_agg(const PartAggParams& p, size_t lds, hipStream_t s);
@@ -1048,6 +1144,10 @@ int32_t filter_plan_class(const ph_query* q, int32_t root, ph_segment* seg);
 bool has_filtered_aggregation(const ph_query* q);
 void filtered_validate(const ph_query* q);  // host-only argument and shape checks of a filtered query
 ph_result* filtered_execute(Context* ctx, const ph_query* q, ph_segment* const* segs, int32_t nseg);
+// variance moments (moments.cpp): a VAR_POP / VAR_SAMP / STDDEV_POP / STDDEV_SAMP somewhere in the query
+bool has_moment_aggregation(const ph_query* q);
+void moments_validate(const ph_query* q);  // host-only argument and shape checks of such a query
+ph_result* moments_execute(Context* ctx, const ph_query* q, ph_segment* const* segs, int32_t nseg);
 // FilterContext.toString of the tree rooted at `root` (FilterContext.java:94-114 and each Predicate.toString)
 std::string filter_to_string(const ph_query* q, int32_t root);
 ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const* segs, int32_t nseg,

@@ -7,7 +7,7 @@ dictionary, DataSchema.fromBytes, fixed-size rows, variable-size data, metadata 
 GroupByDataTableReducer.reduceAndSetResults (core/query/reduce/GroupByDataTableReducer.java:99) /
 AggregationDataTableReducer -- intermediate results merged per group key with AggregationFunction.merge
 (COUNT / SUM add, MIN / MAX, DISTINCTCOUNTHLL HyperLogLog.addAll = register max, DISTINCTCOUNT set union, PERCENTILE
-DoubleArrayList.addAll), then the final results, ORDER BY
+DoubleArrayList.addAll, the variance family VarianceTuple.apply), then the final results, ORDER BY
 and LIMIT (pinot_amd.reduce.reduce_groups).
 """
 from __future__ import annotations
@@ -18,7 +18,8 @@ from typing import Any, Dict, List, Sequence
 
 import numpy as np
 
-from .query import COUNT, DISTINCTCOUNT, DISTINCTCOUNTHLL, MAX, MIN, PERCENTILE, SUM, QueryContext
+from .query import (COUNT, DISTINCTCOUNT, DISTINCTCOUNTHLL, MAX, MIN, PERCENTILE, SUM, VARIANCE_AGGREGATIONS,
+                    QueryContext)
 from .reduce import ResultTable, ValueCounts, merge_intermediate, reduce_groups
 
 # MetadataKey id -> (name, value type) (DataTable.java:103-137); "I" int, "L" long, "S" string
@@ -40,6 +41,7 @@ HLL_OBJECT_TYPE = 6  # ObjectSerDeUtils.ObjectType.HyperLogLog
 # the value sets of DISTINCTCOUNT by stored type (ObjectSerDeUtils.java:113-123)
 SET_OBJECT_TYPES = {9: "INT", 15: "LONG", 16: "FLOAT", 17: "DOUBLE", 18: "STRING"}
 DOUBLE_LIST_OBJECT_TYPE = 3  # ObjectSerDeUtils.ObjectType.DoubleArrayList: PERCENTILE's matched values
+VARIANCE_TUPLE_OBJECT_TYPE = 33  # ObjectSerDeUtils.ObjectType.VarianceTuple (ObjectSerDeUtils.java:137)
 
 
 @dataclass
@@ -124,6 +126,13 @@ def double_list_deserialize(b: bytes) -> ValueCounts:
     if 4 + 8 * n != len(b):
         raise ValueError(f"DoubleArrayList of {n} values takes {4 + 8 * n} bytes, the object has {len(b)}")
     return ValueCounts.of(np.frombuffer(b, ">f8", n, 4).astype(np.float64))
+
+
+def variance_deserialize(b: bytes) -> tuple:
+    """A (count, sum, m2) tuple from VarianceTuple.toBytes (VarianceTuple.java:69-83): long, double, double, BE."""
+    if len(b) != 24:
+        raise ValueError(f"VarianceTuple of {len(b)} bytes")
+    return struct.unpack(">qdd", b)
 
 
 def decode(buf: bytes) -> DataTable:
@@ -217,12 +226,17 @@ def reduce_datatables(q: QueryContext, tables: Sequence[DataTable]) -> ResultTab
                     otype, payload = v
                     assert otype == DOUBLE_LIST_OBJECT_TYPE
                     v = double_list_deserialize(payload)
+                elif a.function in VARIANCE_AGGREGATIONS:
+                    otype, payload = v
+                    assert otype == VARIANCE_TUPLE_OBJECT_TYPE
+                    v = variance_deserialize(payload)
                 inter.append(v)
             if key in groups:
                 groups[key] = [_merge(a.function, x, y) for a, x, y in zip(q.aggregations, groups[key], inter)]
             else:
                 groups[key] = inter
     if not nk and not groups:
-        groups[()] = [0 if a.function == COUNT else None for a in q.aggregations]
+        groups[()] = [0 if a.function == COUNT else ((0, 0.0, 0.0) if a.function in VARIANCE_AGGREGATIONS else None)
+                      for a in q.aggregations]
     keys = list(groups)
     return reduce_groups(q, keys, [groups[k] for k in keys])

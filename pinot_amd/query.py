@@ -29,7 +29,10 @@ COUNT, SUM, MIN, MAX, DISTINCTCOUNTHLL = "COUNT", "SUM", "MIN", "MAX", "DISTINCT
 DISTINCTCOUNT = "DISTINCTCOUNT"  # exact: the size of the value set (DistinctCountAggregationFunction.java:61-68)
 # exact: element (int)(n * p / 100) of the sorted matched values (PercentileAggregationFunction.java:146-158)
 PERCENTILE = "PERCENTILE"
-SUPPORTED_AGGREGATIONS = (COUNT, SUM, MIN, MAX, DISTINCTCOUNTHLL, DISTINCTCOUNT, PERCENTILE)
+# the variance family (VarianceAggregationFunction.java:43-67): a VarianceTuple (count, sum, m2) per result holder
+VARPOP, VARSAMP, STDDEVPOP, STDDEVSAMP = "VARPOP", "VARSAMP", "STDDEVPOP", "STDDEVSAMP"
+VARIANCE_AGGREGATIONS = (VARPOP, VARSAMP, STDDEVPOP, STDDEVSAMP)
+SUPPORTED_AGGREGATIONS = (COUNT, SUM, MIN, MAX, DISTINCTCOUNTHLL, DISTINCTCOUNT, PERCENTILE) + VARIANCE_AGGREGATIONS
 DEFAULT_HLL_LOG2M = 8  # CommonConstants.Helix.DEFAULT_HYPERLOGLOG_LOG2M (CommonConstants.java:96-97)
 DEFAULT_NUM_GROUPS_LIMIT = 100_000  # InstancePlanMakerImplV2.DEFAULT_NUM_GROUPS_LIMIT (:72-73)
 DEFAULT_QUERY_LIMIT = 10
@@ -181,7 +184,7 @@ def parse_percentile(text: str, integer: bool) -> float:
 
 @dataclass(frozen=True)
 class AggregationSpec:
-    function: str           # COUNT | SUM | MIN | MAX | DISTINCTCOUNTHLL | DISTINCTCOUNT | PERCENTILE
+    function: str           # COUNT | SUM | MIN | MAX | DISTINCTCOUNTHLL | DISTINCTCOUNT | PERCENTILE | VARPOP | ...
     column: Optional[str]   # None for COUNT(*); the first operand of an expression
     log2m: int = DEFAULT_HLL_LOG2M
     column2: Optional[str] = None  # second operand of `column <op> column2`
@@ -355,8 +358,14 @@ class _Parser:
                 pct, form = parse_percentile(self.literal(), False), 0
             self.expect("op", ")")
             return AggregationSpec(PERCENTILE, col, DEFAULT_HLL_LOG2M, None, None, pct, form)
-        if t[0] == "id" and n == ("op", "(") and t[1].upper() in SUPPORTED_AGGREGATIONS:
-            fn = t[1].upper()
+        fn = t[1].upper()
+        # the variance family under every spelling the reference accepts: underscores removed, case ignored
+        # (AggregationFunctionType.getNormalizedAggregationFunctionName, AggregationFunctionType.java:424-426), so
+        # VAR_POP, varPop and stddev_samp; the result column name is the type's name in lower case,
+        # `varpop(col)` (BaseSingleInputAggregationFunction.getResultColumnName :43-45), which result_name gives
+        if fn.replace("_", "") in VARIANCE_AGGREGATIONS:
+            fn = fn.replace("_", "")
+        if t[0] == "id" and n == ("op", "(") and fn in SUPPORTED_AGGREGATIONS:
             self.i += 2
             col2 = op = None
             if self.accept("op", "*"):
@@ -372,8 +381,8 @@ class _Parser:
                         raise SqlParseError(f"expressions are supported in SUM/MIN/MAX, not {fn}")
             log2m = DEFAULT_HLL_LOG2M
             if self.accept("op", ","):
-                if fn == DISTINCTCOUNT:
-                    raise SqlParseError("DISTINCTCOUNT takes one argument")
+                if fn == DISTINCTCOUNT or fn in VARIANCE_AGGREGATIONS:
+                    raise SqlParseError(f"{fn} takes one argument")
                 log2m = int(self.literal())
             self.expect("op", ")")
             if fn != COUNT and col is None:

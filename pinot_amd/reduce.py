@@ -5,7 +5,9 @@ Mirrors the final steps the reference applies after the server-side combine:
 * ``AggregationFunction.extractFinalResult`` -- COUNT -> long, SUM/MIN/MAX -> double,
   DISTINCTCOUNTHLL -> ``HyperLogLog.cardinality()`` (DistinctCountHLLAggregationFunction.java:362-364),
   DISTINCTCOUNT -> the value set's size as int (DistinctCountAggregationFunction.java:61-68),
-  PERCENTILE -> element (int)(n * p / 100) of the sorted values (PercentileAggregationFunction.java:146-158).
+  PERCENTILE -> element (int)(n * p / 100) of the sorted values (PercentileAggregationFunction.java:146-158),
+  VARPOP / VARSAMP / STDDEVPOP / STDDEVSAMP -> m2 / count or m2 / (count - 1), its square root for STDDEV
+  (VarianceAggregationFunction.java:228-248).
 * ``IndexedTable.finish`` / ``GroupByDataTableReducer.reduceAndSetResults`` -- ORDER BY over group-by
   columns and aggregations (ASC/DESC), then LIMIT (core/data/table/IndexedTable.java:148-173,
   core/query/reduce/GroupByDataTableReducer.java:99).
@@ -23,7 +25,8 @@ from typing import Any, List, Sequence
 
 import numpy as np
 
-from .query import COUNT, DISTINCTCOUNT, DISTINCTCOUNTHLL, MAX, MIN, PERCENTILE, SUM, QueryContext
+from .query import (COUNT, DISTINCTCOUNT, DISTINCTCOUNTHLL, MAX, MIN, PERCENTILE, STDDEVPOP, STDDEVSAMP, SUM,
+                    VARIANCE_AGGREGATIONS, VARSAMP, QueryContext)
 
 
 def _java_round(x: float) -> int:
@@ -133,6 +136,34 @@ def double_list_serialize(vc: ValueCounts) -> bytes:
     return np.array([vc.size], dtype=">i4").tobytes() + vc.sorted_values().astype(">f8").tobytes()
 
 
+def variance_merge(a, b) -> tuple:
+    """VarianceTuple.apply(VarianceTuple) (VarianceTuple.java:46-55) on (count, sum, m2) tuples, in its order of
+    operations: ``b`` merged into ``a``; a zero count on either side adds nothing."""
+    (n1, s1, m1), (n2, s2, m2) = a, b
+    if n2 == 0:
+        return (int(n1), float(s1), float(m1))
+    avg = 0.0 if n1 == 0 else float(s1) / float(n1)
+    delta = float(s2) / float(n2) - avg
+    return (int(n1) + int(n2), float(s1) + float(s2),
+            float(m1) + (float(m2) + delta * delta * float(n2) * float(n1) / float(int(n2) + int(n1))))
+
+
+def variance_final(t, function: str) -> float:
+    """VarianceAggregationFunction.extractFinalResult (:228-248): -Infinity for count 0 and for a sample function with
+    count 1, else m2 / count (population) or m2 / (count - 1) (sample), its square root for the STDDEV functions."""
+    n, _, m2 = t
+    sample = function in (VARSAMP, STDDEVSAMP)
+    if n == 0 or (sample and n == 1):
+        return float("-inf")
+    v = float(m2) / float(n - 1 if sample else n)
+    return math.sqrt(v) if function in (STDDEVPOP, STDDEVSAMP) else v
+
+
+def variance_serialize(t) -> bytes:
+    """VarianceTuple.toBytes (VarianceTuple.java:69-75): long count, double sum, double m2, big-endian."""
+    return struct.pack(">qdd", int(t[0]), float(t[1]), float(t[2]))
+
+
 def _double_compare_key(x) -> int:
     """An int whose order is Double.compare's (NaN largest, -0.0 < 0.0)."""
     x = float(x)
@@ -172,6 +203,8 @@ def merge_intermediate(function: str, a, b):
         return frozenset(a) | frozenset(b)
     if function == PERCENTILE:
         return a.merge(b)
+    if function in VARIANCE_AGGREGATIONS:
+        return variance_merge(a, b)
     return np.maximum(a, b)  # HyperLogLog.addAll
 
 
@@ -193,6 +226,8 @@ def final_value(spec, value):
         return len(value)
     if spec.function == PERCENTILE:
         return percentile_final(value, spec.percentile)
+    if spec.function in VARIANCE_AGGREGATIONS:
+        return variance_final(value, spec.function)
     return float(value)
 
 
