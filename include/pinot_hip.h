@@ -200,7 +200,43 @@ typedef struct {
  *   - a call in which a segment could reach num_groups_limit (min(product of the group-by cardinalities, docs) >= the
  *     limit);
  *   - key spaces beyond 2^40 keys or the dense table budget (8 + 48 bytes x distinct columns per key over 32 GB);
- *   - more than 4 distinct argument columns. */
+ *   - more than 4 distinct argument columns.
+ *
+ * PH_AGG_COVARPOP / PH_AGG_COVARSAMP: the reference's CovarianceAggregationFunction over two pinned single-value INT,
+ * LONG, FLOAT or DOUBLE columns (raw columns too): `column` is x and `column2` is y, with expr_op PH_EXPR_NONE (the field
+ * of the 2-operand terms carries the second argument).  The intermediate result of a row is the reference's
+ * CovarianceTuple of the row's `count` matched docs (CovarianceAggregationFunction.java:95-140): 32 bytes in host
+ * order, {double sum_x; double sum_y; double sum_xy; int64 count}; a row with no doc holds (0.0, 0.0, 0.0, 0), which
+ * only an aggregation-only query that matched nothing returns (:155-162).  The two functions over one ordered pair
+ * return the same tuple and differ in the final result (:185-201: -Infinity for count 0 and for the sample function
+ * with count 1, else sum_xy / count - sum_x sum_y / (count count), or sum_xy / (count - 1) - sum_x sum_y /
+ * (count (count - 1))) and in the result column name, `covarpop(x,y)`.  (x, y) and (y, x) are different pairs.  The
+ * reference adds in doubles, doc by doc; here the scan adds n, sum(dx), sum(dy) and sum(dx dy) of dx = x - Kx,
+ * dy = y - Ky, with Kx, Ky the smallest value of each column over the queried segments, rx, ry the columns' ranges
+ * and N the docs of the call's segments:
+ *   - both columns stored as INT or LONG, rx N < 2^64, ry N < 2^64 and rx ry N < 2^128: exact unsigned integer sums,
+ *     sum(dx dy) in one 64-bit cell when rx ry N < 2^64 and in 128 bits otherwise.  Then sum_x = n Kx + sum(dx), sum_y
+ *     likewise and sum_xy = sum(dx dy) + Ky sum(dx) + Kx sum(dy) + n Kx Ky are formed exactly and rounded once each:
+ *     every component is the correctly rounded exact sum, independent of the order of the docs and bit-reproducible;
+ *   - a FLOAT / DOUBLE column in the pair, or integer columns past those bounds: the unshifted values and the three
+ *     sums in double (order-dependent, as a DOUBLE SUM: within 1e-9 relative of the sum of the terms' magnitudes).
+ * Served: queries whose aggregations are all of this family or COUNT(*), with or without a WHERE clause and a GROUP BY,
+ * any number of such aggregations over at most 4 distinct ordered pairs.  log2m and percentile are ignored.
+ * ph_exec_stats.scan_kernel is PH_KERNEL_SCAN_COMOMENTS; plan_mode 1 / 2 / 3.  num_docs_scanned is the matched docs,
+ * num_entries_scanned_in_filter the WHERE clause's ordinary statistic, num_entries_scanned_post_filter the matched docs
+ * x (group-by columns + distinct argument columns).  Never answered from a star-tree or from metadata.  A call without
+ * column2 is PH_ERR_BAD_QUERY.  Shapes that return PH_ERR_UNSUPPORTED, each with its own message (the CPU plan serves
+ * them):
+ *   - a STRING column, a sketch column or a non-NONE expr_op (an expression argument);
+ *   - any other aggregation beside a function of the family: SUM / MIN / MAX / DISTINCTCOUNTHLL / DISTINCTCOUNT /
+ *     PERCENTILE, and the variance family ("variance function beside a covariance function");
+ *   - a FILTER clause on or beside one;
+ *   - multi-device contexts and the dense-partial entry points;
+ *   - segment group trim (min_segment_group_trim_size > 0 with ORDER BY);
+ *   - a call in which a segment could reach num_groups_limit (min(product of the group-by cardinalities, docs) >= the
+ *     limit);
+ *   - key spaces beyond 2^40 keys or the dense table budget (8 + 64 bytes x distinct pairs per key over 32 GB);
+ *   - more than 4 distinct ordered pairs. */
 typedef enum {
   PH_AGG_COUNT = 0,
   PH_AGG_SUM = 1,
@@ -212,7 +248,9 @@ typedef enum {
   PH_AGG_VARPOP = 7,
   PH_AGG_VARSAMP = 8,
   PH_AGG_STDDEVPOP = 9,
-  PH_AGG_STDDEVSAMP = 10
+  PH_AGG_STDDEVSAMP = 10,
+  PH_AGG_COVARPOP = 11,
+  PH_AGG_COVARSAMP = 12
 } ph_aggregation_type;
 
 /* 2-operand expression argument of SUM / MIN / MAX: `column <op> column2`, evaluated per row like the reference's
@@ -225,7 +263,8 @@ typedef struct {
   int32_t type;                 /* ph_aggregation_type */
   const char* column;           /* NULL for COUNT(*); first operand of an expression */
   int32_t log2m;                /* DISTINCTCOUNTHLL; 0 = default 8 (CommonConstants.java:96-97) */
-  const char* column2;          /* second operand (expr_op != PH_EXPR_NONE), else NULL */
+  const char* column2;          /* second operand (expr_op != PH_EXPR_NONE); the second argument of COVARPOP /
+                                   COVARSAMP (expr_op PH_EXPR_NONE); else NULL */
   int32_t expr_op;              /* ph_expr_op */
   double percentile;            /* PERCENTILE: 0..100; 0 for every other type */
   int32_t percentile_name_form; /* PERCENTILE: 0 = `percentile(col, 90.0)`, 1 = `percentile90(col)`: the result column
@@ -359,8 +398,10 @@ enum {
                                        table, equal (row, id) lanes of a wave combined first (plan_mode 1 or 3) */
   PH_KERNEL_SCAN_FILTERED = 20,     /* k_scan_filtered<MODE>: filtered aggregations, every pipeline's doc bitmap applied
                                        in one pass over the group-by and value columns (plan_mode 1, 2 or 3) */
-  PH_KERNEL_SCAN_MOMENTS = 21       /* k_scan_moments<MODE, FORM> + k_moments_finish: the variance family as exact shifted
+  PH_KERNEL_SCAN_MOMENTS = 21,      /* k_scan_moments<MODE, FORM> + k_moments_finish: the variance family as exact shifted
                                        moments (plan_mode 1, 2 or 3 as the tables live in registers, LDS or HBM) */
+  PH_KERNEL_SCAN_COMOMENTS = 22     /* k_scan_comoments<MODE, FORM, C> + k_comoments_finish: COVAR_POP / COVAR_SAMP as
+                                       exact shifted co-moments over a register-direct decode (plan_mode 1, 2 or 3) */
 };
 
 /* ------------------------------------------------------------------ context */
@@ -514,7 +555,8 @@ const void* ph_result_key_data(const ph_result* r, int32_t group_by_index);
  * i >> 5 set means value i of the dictionary is present; bits past D are zero,
  * PERCENTILE uint32[D] histogram over the aggregation's result dictionary: the matched docs of each value
  * (PERCENTILE aggregations over one column return the same histogram),
- * VARPOP / VARSAMP / STDDEVPOP / STDDEVSAMP {int64 count; double sum; double m2}, 24 bytes (see PH_AGG_VARPOP) */
+ * VARPOP / VARSAMP / STDDEVPOP / STDDEVSAMP {int64 count; double sum; double m2}, 24 bytes (see PH_AGG_VARPOP),
+ * COVARPOP / COVARSAMP {double sum_x; double sum_y; double sum_xy; int64 count}, 32 bytes (see PH_AGG_COVARPOP) */
 int ph_result_aggregation(const ph_result* r, int32_t aggregation_index, void* out);
 const void* ph_result_aggregation_data(const ph_result* r, int32_t aggregation_index);
 /* DISTINCTCOUNT aggregation k.  Its result dictionary is the table dictionary of the column (ph_table_set_dictionary)

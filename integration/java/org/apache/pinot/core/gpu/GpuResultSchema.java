@@ -60,6 +60,9 @@ final class GpuResultSchema {
       case STDDEVPOP:
       case STDDEVSAMP:
         return new VarianceColumn(res, k);
+      case COVARPOP:
+      case COVARSAMP:
+        return new CovarianceColumn(res, k);
       default:
         return null;
     }
@@ -80,6 +83,24 @@ final class GpuResultSchema {
       int at = 24 * row;
       return new org.apache.pinot.segment.local.customobject.VarianceTuple(_rows.getLong(at), _rows.getDouble(at + 8),
           _rows.getDouble(at + 16));
+    }
+  }
+
+  /** COVAR_POP / COVAR_SAMP aggregation {@code k} of a result: 32-byte rows in host order, {double sumX; double sumY;
+   *  double sumXY; long count} -- the CovarianceTuple the function's intermediate column (OBJECT,
+   *  CovarianceAggregationFunction.java:175-178) holds. */
+  static final class CovarianceColumn implements RowObjects {
+    private final ByteBuffer _rows;
+
+    CovarianceColumn(long res, int k) {
+      _rows = PinotHipJni.resultAggregationBuffer(res, k, 32).order(ByteOrder.nativeOrder());
+    }
+
+    @Override
+    public Object row(int row) {
+      int at = 32 * row;
+      return new org.apache.pinot.segment.local.customobject.CovarianceTuple(_rows.getDouble(at),
+          _rows.getDouble(at + 8), _rows.getDouble(at + 16), _rows.getLong(at + 24));
     }
   }
 

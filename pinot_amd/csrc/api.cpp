@@ -346,6 +346,12 @@ int ph_query_execute(ph_ctx* ctx, const ph_query* query, ph_segment* const* segm
       if (query->min_segment_group_trim_size > 0 && query->num_group_by > 0 && query->num_order_by > 0)
         fail(PH_ERR_UNSUPPORTED, std::string(fn) + " with segment group trim (minSegmentGroupTrimSize)");
     }
+    if (has_comoment_aggregation(query)) {  // their own plan (comoments.cpp): exact shifted co-moments
+      comoments_validate(query);
+      if (ctx->devs.size() > 1) fail(PH_ERR_UNSUPPORTED, "covariance functions on a multi-device context");
+      *out = comoments_execute(&ctx->c, query, segments, num_segments);
+      return;
+    }
     if (has_moment_aggregation(query)) {  // their own plan (moments.cpp): exact shifted moments, one finish kernel
       moments_validate(query);
       if (ctx->devs.size() > 1) fail(PH_ERR_UNSUPPORTED, "variance functions on a multi-device context");
@@ -442,6 +448,10 @@ static Context* dense_device(ph_ctx* ctx, ph_segment* const* segs, int32_t n) {
 }
 
 static void reject_dense_shapes(const ph_query* q) {
+  if (has_comoment_aggregation(q)) {
+    comoments_validate(q);
+    fail(PH_ERR_UNSUPPORTED, "covariance functions on dense partials");
+  }
   if (has_moment_aggregation(q)) {
     moments_validate(q);
     fail(PH_ERR_UNSUPPORTED, "variance functions on dense partials");

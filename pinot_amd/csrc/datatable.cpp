@@ -130,9 +130,11 @@ std::string agg_column_name(const ph_aggregation& a) {
   // (the variance family: getType().getName().toLowerCase(), BaseSingleInputAggregationFunction.java:43-45 over
   // AggregationFunctionType.java:174-181)
   static const char* fn[] = {"count", "sum", "min", "max", "distinctcounthll", "distinctcount", "percentile",
-                             "varpop", "varsamp", "stddevpop", "stddevsamp"};
-  if (a.type < 0 || a.type > PH_AGG_STDDEVSAMP) fail(PH_ERR_INVALID_ARGUMENT, "unknown aggregation");
+                             "varpop", "varsamp", "stddevpop", "stddevsamp", "covarpop", "covarsamp"};
+  if (a.type < 0 || a.type > PH_AGG_COVARSAMP) fail(PH_ERR_INVALID_ARGUMENT, "unknown aggregation");
   if (a.type == PH_AGG_COUNT) return "count(*)";
+  if (a.type == PH_AGG_COVARPOP || a.type == PH_AGG_COVARSAMP)  // CovarianceAggregationFunction.getResultColumnName
+    return std::string(fn[a.type]) + "(" + (a.column ? a.column : "") + "," + (a.column2 ? a.column2 : "") + ")";  // (:72-74)
   if (a.type == PH_AGG_PERCENTILE) {  // PercentileAggregationFunction.getResultColumnName (:60-64)
     const std::string col = a.column ? a.column : "";
     if (a.percentile_name_form) return std::string(fn[a.type]) + std::to_string((int)a.percentile) + "(" + col + ")";
@@ -245,6 +247,15 @@ std::vector<uint8_t> result_to_datatable(const ph_result* r, const ph_query* q, 
         put_be(dst, (uint32_t)var.b.size(), 4);
         put_be(dst + 4, 24u, 4);
         var.i32(33);
+        for (uint64_t x : f) var.i64((int64_t)x);
+      } else if (t == PH_AGG_COVARPOP || t == PH_AGG_COVARSAMP) {
+        // CovarianceTuple.toBytes as ObjectType.CovarianceTuple (ObjectSerDeUtils.java:136): double sumX, double sumY,
+        // double sumXY, long count, big-endian
+        uint64_t f[4];
+        memcpy(f, base + (size_t)g * 32, 32);
+        put_be(dst, (uint32_t)var.b.size(), 4);
+        put_be(dst + 4, 32u, 4);
+        var.i32(32);
         for (uint64_t x : f) var.i64((int64_t)x);
       } else if (t == PH_AGG_PERCENTILE) {
         // the DoubleArrayList of the matched values (ObjectSerDeUtils.java:328-357): int objectType 3, int size, the

@@ -495,6 +495,72 @@ size_t moments_lds_bytes(const MParams& p, int mode, int form);
 void launch_scan_moments(const MParams& p, int mode, int form, int grid, hipStream_t s);
 void launch_moments_finish(const MFinishParams& p, hipStream_t s);
 
+// Co-moments (scan_comoments.hip, comoments.cpp): COVAR_POP / COVAR_SAMP.  A slot is one ordered pair of argument
+// columns (x, y); per group it accumulates S1x = sum(dx), S1y = sum(dy) and Sxy = sum(dx dy) of dx = x - Kx, dy = y - Ky
+// (Kx, Ky: the smallest value of the column over the call's segments, so dx, dy >= 0), beside the docs n of the group.
+constexpr int kCMaxSlots = 4;  // distinct ordered pairs of one query
+enum : int32_t {
+  CFORM_NARROW = 0,  // u64 dx, dy; Sxy in one u64 cell (rx ry docs < 2^64: never carries)
+  CFORM_WIDE = 1,    // u64 dx, dy; Sxy in a (lo, hi) pair of u64 cells
+  CFORM_REAL = 2,    // x, y unshifted doubles; the three sums are doubles
+};
+struct CPair {
+  const uint32_t* xfwd;                           // packed dictIds of x and of y, their widths
+  const uint32_t* yfwd;
+  const unsigned long long* x_of;                 // [dictId]: x - Kx as a u64, or the bits of (double) x (CFORM_REAL)
+  const unsigned long long* y_of;
+  int32_t xbits, ybits;
+};
+struct CSegment {
+  int32_t num_docs;
+  const unsigned long long* mask;                 // the WHERE clause's doc bitmap (bit i of word w = doc 64 w + i);
+                                                  //   nullptr = every doc
+  const uint32_t* gfwd[kMaxGroupCols];            // group-by column g: packed dictIds, their width, dictId -> key id
+  const int32_t* gremap[kMaxGroupCols];           //   (nullptr: identity)
+  int32_t gbits[kMaxGroupCols];
+  CPair pair[kCMaxSlots];
+};
+struct CSlot {                                    // one slot of a launch: its CSegment pair and its [num_groups] tables
+  int32_t pair;
+  unsigned long long* s1x;
+  unsigned long long* s1y;
+  unsigned long long* sxy;
+  unsigned long long* sxyhi;                      // CFORM_WIDE only
+};
+struct CParams {
+  const CSegment* segs;
+  const Chunk* chunks;
+  const CSlot* slots;                             // device memory, [num_slots]
+  int32_t chunk_begin, chunk_end;
+  int32_t num_slots, num_group_cols;
+  uint32_t group_stride[kMaxGroupCols];
+  int64_t num_groups;                             // dense key space (1 without a group-by), < 2^32
+  // zeroed tables; n [num_groups] and seg_count (docs per segment) are nullptr in a call's second and third launch
+  unsigned long long* n;
+  unsigned long long* seg_count;
+};
+// k_comoments_finish: one thread per (group, slot) turns (n, S1x, S1y, Sxy) into the reference's CovarianceTuple
+struct CTuple {
+  double sum_x, sum_y, sum_xy;
+  int64_t count;
+};
+struct CFinishParams {
+  int64_t num_groups;
+  int32_t num_slots;
+  int32_t form[kCMaxSlots];
+  int64_t kx[kCMaxSlots], ky[kCMaxSlots];         // the shifts (integer forms)
+  const unsigned long long* n;
+  const unsigned long long* s1x[kCMaxSlots];
+  const unsigned long long* s1y[kCMaxSlots];
+  const unsigned long long* sxy[kCMaxSlots];
+  const unsigned long long* sxyhi[kCMaxSlots];
+  CTuple* out[kCMaxSlots];                        // [num_groups]
+};
+size_t comoments_lds_bytes(const CParams& p, int mode, int form);
+// `max_bits`: the widest packed stream (group-by and argument columns) of the launch's segments
+void launch_scan_comoments(const CParams& p, int mode, int form, int max_bits, int grid, hipStream_t s);
+void launch_comoments_finish(const CFinishParams& p, hipStream_t s);
+
 // Kernel B of the partitioned group-by: aggregates one batch of records per partition in LDS, then merges
 // the partition's key range into the dense result table (each key range has exactly one owner block).
 struct PartAggParams {
@@ -1148,6 +1214,10 @@ ph_result* filtered_execute(Context* ctx, const ph_query* q, ph_segment* const* 
 bool has_moment_aggregation(const ph_query* q);
 void moments_validate(const ph_query* q);  // host-only argument and shape checks of such a query
 ph_result* moments_execute(Context* ctx, const ph_query* q, ph_segment* const* segs, int32_t nseg);
+// co-moments (comoments.cpp): a COVAR_POP / COVAR_SAMP somewhere in the query
+bool has_comoment_aggregation(const ph_query* q);
+void comoments_validate(const ph_query* q);  // host-only argument and shape checks of such a query
+ph_result* comoments_execute(Context* ctx, const ph_query* q, ph_segment* const* segs, int32_t nseg);
 // FilterContext.toString of the tree rooted at `root` (FilterContext.java:94-114 and each Predicate.toString)
 std::string filter_to_string(const ph_query* q, int32_t root);
 ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const* segs, int32_t nseg,

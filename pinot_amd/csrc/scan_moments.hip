@@ -21,6 +21,7 @@
 // The docs matched per segment (wave-uniform popcounts, one atomic per chunk and wave) give the statistics.
 #include <algorithm>
 
+#include "limbs_to_double.h"
 #include "scan_kernel.h"
 
 namespace ph {
@@ -222,43 +223,6 @@ __global__ void __launch_bounds__(kBlock) k_scan_moments(const MParams p) {
 }
 
 // ---- finish: (n, S1, S2) -> VarianceTuple
-
-// a 256-bit unsigned integer (four u64 limbs, x[0] lowest) to double, round-to-nearest-even
-__device__ __forceinline__ double m_limbs_to_double(const u64 (&x)[4]) {
-  int top = -1;
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-    if (x[i]) top = 64 * i + 63 - __clzll((long long)x[i]);
-  if (top < 53) return (double)x[0];  // (exact; also the zero)
-  const int shift = top - 52;         // the mantissa is bits [shift, shift + 53)
-  // the 64 bits from bit `shift` up (nothing above `top` is set) and the bits below it
-  const int li = shift >> 6, off = shift & 63;
-  u64 a = 0ull, b = 0ull, below = 0ull;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    if (k == li) a = x[k];
-    if (k == li + 1) b = x[k];
-    if (k < li) below |= x[k];
-  }
-  u64 mant = off ? (a >> off) | (b << (64 - off)) : a;
-  const u64 rest = off ? a << (64 - off) : 0ull;  // the bits of limb li below `shift`, left-aligned
-  bool round_bit, sticky;
-  if (off) {
-    round_bit = (rest >> 63) != 0ull;
-    sticky = (rest << 1) != 0ull || below != 0ull;
-  } else {  // the round bit is the top bit of limb li - 1 (li >= 1 here: shift >= 64)
-    u64 prev = 0ull, lower = 0ull;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      if (k == li - 1) prev = x[k];
-      if (k < li - 1) lower |= x[k];
-    }
-    round_bit = (prev >> 63) != 0ull;
-    sticky = (prev << 1) != 0ull || lower != 0ull;
-  }
-  if (round_bit && (sticky || (mant & 1ull))) mant += 1ull;
-  return ldexp((double)mant, shift);  // mant <= 2^53: exact, and so is the scaling
-}
 
 __global__ void __launch_bounds__(256) k_moments_finish(const MFinishParams p) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;

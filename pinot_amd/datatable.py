@@ -7,7 +7,7 @@ dictionary, DataSchema.fromBytes, fixed-size rows, variable-size data, metadata 
 GroupByDataTableReducer.reduceAndSetResults (core/query/reduce/GroupByDataTableReducer.java:99) /
 AggregationDataTableReducer -- intermediate results merged per group key with AggregationFunction.merge
 (COUNT / SUM add, MIN / MAX, DISTINCTCOUNTHLL HyperLogLog.addAll = register max, DISTINCTCOUNT set union, PERCENTILE
-DoubleArrayList.addAll, the variance family VarianceTuple.apply), then the final results, ORDER BY
+DoubleArrayList.addAll, the variance family VarianceTuple.apply, COVARPOP / COVARSAMP CovarianceTuple.apply), then the final results, ORDER BY
 and LIMIT (pinot_amd.reduce.reduce_groups).
 """
 from __future__ import annotations
@@ -18,8 +18,8 @@ from typing import Any, Dict, List, Sequence
 
 import numpy as np
 
-from .query import (COUNT, DISTINCTCOUNT, DISTINCTCOUNTHLL, MAX, MIN, PERCENTILE, SUM, VARIANCE_AGGREGATIONS,
-                    QueryContext)
+from .query import (COUNT, COVARIANCE_AGGREGATIONS, DISTINCTCOUNT, DISTINCTCOUNTHLL, MAX, MIN, PERCENTILE, SUM,
+                    VARIANCE_AGGREGATIONS, QueryContext)
 from .reduce import ResultTable, ValueCounts, merge_intermediate, reduce_groups
 
 # MetadataKey id -> (name, value type) (DataTable.java:103-137); "I" int, "L" long, "S" string
@@ -42,6 +42,7 @@ HLL_OBJECT_TYPE = 6  # ObjectSerDeUtils.ObjectType.HyperLogLog
 SET_OBJECT_TYPES = {9: "INT", 15: "LONG", 16: "FLOAT", 17: "DOUBLE", 18: "STRING"}
 DOUBLE_LIST_OBJECT_TYPE = 3  # ObjectSerDeUtils.ObjectType.DoubleArrayList: PERCENTILE's matched values
 VARIANCE_TUPLE_OBJECT_TYPE = 33  # ObjectSerDeUtils.ObjectType.VarianceTuple (ObjectSerDeUtils.java:137)
+COVARIANCE_TUPLE_OBJECT_TYPE = 32  # ObjectSerDeUtils.ObjectType.CovarianceTuple (ObjectSerDeUtils.java:136)
 
 
 @dataclass
@@ -133,6 +134,13 @@ def variance_deserialize(b: bytes) -> tuple:
     if len(b) != 24:
         raise ValueError(f"VarianceTuple of {len(b)} bytes")
     return struct.unpack(">qdd", b)
+
+
+def covariance_deserialize(b: bytes) -> tuple:
+    """A (sum_x, sum_y, sum_xy, count) tuple from CovarianceTuple.toBytes: double, double, double, long, BE."""
+    if len(b) != 32:
+        raise ValueError(f"CovarianceTuple of {len(b)} bytes")
+    return struct.unpack(">dddq", b)
 
 
 def decode(buf: bytes) -> DataTable:
@@ -230,13 +238,18 @@ def reduce_datatables(q: QueryContext, tables: Sequence[DataTable]) -> ResultTab
                     otype, payload = v
                     assert otype == VARIANCE_TUPLE_OBJECT_TYPE
                     v = variance_deserialize(payload)
+                elif a.function in COVARIANCE_AGGREGATIONS:
+                    otype, payload = v
+                    assert otype == COVARIANCE_TUPLE_OBJECT_TYPE
+                    v = covariance_deserialize(payload)
                 inter.append(v)
             if key in groups:
                 groups[key] = [_merge(a.function, x, y) for a, x, y in zip(q.aggregations, groups[key], inter)]
             else:
                 groups[key] = inter
     if not nk and not groups:
-        groups[()] = [0 if a.function == COUNT else ((0, 0.0, 0.0) if a.function in VARIANCE_AGGREGATIONS else None)
-                      for a in q.aggregations]
+        empty = {f: (0, 0.0, 0.0) for f in VARIANCE_AGGREGATIONS}
+        empty.update({f: (0.0, 0.0, 0.0, 0) for f in COVARIANCE_AGGREGATIONS}, COUNT=0)
+        groups[()] = [empty.get(a.function) for a in q.aggregations]
     keys = list(groups)
     return reduce_groups(q, keys, [groups[k] for k in keys])

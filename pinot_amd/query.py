@@ -32,7 +32,12 @@ PERCENTILE = "PERCENTILE"
 # the variance family (VarianceAggregationFunction.java:43-67): a VarianceTuple (count, sum, m2) per result holder
 VARPOP, VARSAMP, STDDEVPOP, STDDEVSAMP = "VARPOP", "VARSAMP", "STDDEVPOP", "STDDEVSAMP"
 VARIANCE_AGGREGATIONS = (VARPOP, VARSAMP, STDDEVPOP, STDDEVSAMP)
-SUPPORTED_AGGREGATIONS = (COUNT, SUM, MIN, MAX, DISTINCTCOUNTHLL, DISTINCTCOUNT, PERCENTILE) + VARIANCE_AGGREGATIONS
+# COVAR_POP(x, y) / COVAR_SAMP(x, y) (CovarianceAggregationFunction.java:51-69): a CovarianceTuple (sumX, sumY, sumXY,
+# count) per result holder
+COVARPOP, COVARSAMP = "COVARPOP", "COVARSAMP"
+COVARIANCE_AGGREGATIONS = (COVARPOP, COVARSAMP)
+SUPPORTED_AGGREGATIONS = ((COUNT, SUM, MIN, MAX, DISTINCTCOUNTHLL, DISTINCTCOUNT, PERCENTILE) + VARIANCE_AGGREGATIONS
+                          + COVARIANCE_AGGREGATIONS)
 DEFAULT_HLL_LOG2M = 8  # CommonConstants.Helix.DEFAULT_HYPERLOGLOG_LOG2M (CommonConstants.java:96-97)
 DEFAULT_NUM_GROUPS_LIMIT = 100_000  # InstancePlanMakerImplV2.DEFAULT_NUM_GROUPS_LIMIT (:72-73)
 DEFAULT_QUERY_LIMIT = 10
@@ -187,7 +192,7 @@ class AggregationSpec:
     function: str           # COUNT | SUM | MIN | MAX | DISTINCTCOUNTHLL | DISTINCTCOUNT | PERCENTILE | VARPOP | ...
     column: Optional[str]   # None for COUNT(*); the first operand of an expression
     log2m: int = DEFAULT_HLL_LOG2M
-    column2: Optional[str] = None  # second operand of `column <op> column2`
+    column2: Optional[str] = None  # second operand of `column <op> column2`; the second argument of COVARPOP / COVARSAMP
     op: Optional[str] = None       # "*", "-" or "+" (None: plain column)
     percentile: float = 0.0        # PERCENTILE: 0..100
     name_form: int = 0             # PERCENTILE: 1 for the `PERCENTILEnn(col)` spelling (the result column name only)
@@ -205,6 +210,8 @@ class AggregationSpec:
         arg = "*" if self.column is None else self.column
         if self.op:
             arg = f"{EXPR_OPS[self.op]}({self.column},{self.column2})"
+        elif self.function in COVARIANCE_AGGREGATIONS:  # no space after the comma (getResultColumnName :72-74)
+            arg = f"{self.column},{self.column2}"
         if self.function == PERCENTILE:  # PercentileAggregationFunction.getResultColumnName (:60-64)
             if self.name_form:
                 return f"percentile{int(self.percentile)}({arg})"
@@ -363,7 +370,7 @@ class _Parser:
         # (AggregationFunctionType.getNormalizedAggregationFunctionName, AggregationFunctionType.java:424-426), so
         # VAR_POP, varPop and stddev_samp; the result column name is the type's name in lower case,
         # `varpop(col)` (BaseSingleInputAggregationFunction.getResultColumnName :43-45), which result_name gives
-        if fn.replace("_", "") in VARIANCE_AGGREGATIONS:
+        if fn.replace("_", "") in VARIANCE_AGGREGATIONS + COVARIANCE_AGGREGATIONS:
             fn = fn.replace("_", "")
         if t[0] == "id" and n == ("op", "(") and fn in SUPPORTED_AGGREGATIONS:
             self.i += 2
@@ -380,7 +387,16 @@ class _Parser:
                     if fn not in (SUM, MIN, MAX):
                         raise SqlParseError(f"expressions are supported in SUM/MIN/MAX, not {fn}")
             log2m = DEFAULT_HLL_LOG2M
-            if self.accept("op", ","):
+            if fn in COVARIANCE_AGGREGATIONS:
+                # two plain columns: the reference reads arguments.get(0) and get(1) with no check of its own
+                # (CovarianceAggregationFunction.java:57-61), so one argument fails there; its operand checker declares
+                # two NUMERIC operands (AggregationFunctionType.java:168-173), which a third one misses
+                if col is None or not self.accept("op", ","):
+                    raise SqlParseError(f"{fn} takes two arguments")
+                col2 = self.ident()
+                if not (self.peek() == ("op", ")")):
+                    raise SqlParseError(f"{fn} takes two column arguments")
+            elif self.accept("op", ","):
                 if fn == DISTINCTCOUNT or fn in VARIANCE_AGGREGATIONS:
                     raise SqlParseError(f"{fn} takes one argument")
                 log2m = int(self.literal())

@@ -7,7 +7,9 @@ Mirrors the final steps the reference applies after the server-side combine:
   DISTINCTCOUNT -> the value set's size as int (DistinctCountAggregationFunction.java:61-68),
   PERCENTILE -> element (int)(n * p / 100) of the sorted values (PercentileAggregationFunction.java:146-158),
   VARPOP / VARSAMP / STDDEVPOP / STDDEVSAMP -> m2 / count or m2 / (count - 1), its square root for STDDEV
-  (VarianceAggregationFunction.java:228-248).
+  (VarianceAggregationFunction.java:228-248),
+  COVARPOP / COVARSAMP -> sumXY / count - sumX sumY / (count count), or its sample form
+  (CovarianceAggregationFunction.java:185-201).
 * ``IndexedTable.finish`` / ``GroupByDataTableReducer.reduceAndSetResults`` -- ORDER BY over group-by
   columns and aggregations (ASC/DESC), then LIMIT (core/data/table/IndexedTable.java:148-173,
   core/query/reduce/GroupByDataTableReducer.java:99).
@@ -25,8 +27,8 @@ from typing import Any, List, Sequence
 
 import numpy as np
 
-from .query import (COUNT, DISTINCTCOUNT, DISTINCTCOUNTHLL, MAX, MIN, PERCENTILE, STDDEVPOP, STDDEVSAMP, SUM,
-                    VARIANCE_AGGREGATIONS, VARSAMP, QueryContext)
+from .query import (COUNT, COVARIANCE_AGGREGATIONS, COVARSAMP, DISTINCTCOUNT, DISTINCTCOUNTHLL, MAX, MIN, PERCENTILE,
+                    STDDEVPOP, STDDEVSAMP, SUM, VARIANCE_AGGREGATIONS, VARSAMP, QueryContext)
 
 
 def _java_round(x: float) -> int:
@@ -164,6 +166,29 @@ def variance_serialize(t) -> bytes:
     return struct.pack(">qdd", int(t[0]), float(t[1]), float(t[2]))
 
 
+def covariance_merge(a, b) -> tuple:
+    """CovarianceTuple.apply(CovarianceTuple) on (sum_x, sum_y, sum_xy, count) tuples: the components add."""
+    return (float(a[0]) + float(b[0]), float(a[1]) + float(b[1]), float(a[2]) + float(b[2]), int(a[3]) + int(b[3]))
+
+
+def covariance_final(t, function: str) -> float:
+    """CovarianceAggregationFunction.extractFinalResult (:185-201), in its order of operations (the counts multiply as
+    integers before they divide): -Infinity for count 0 and for the sample function with count 1."""
+    sum_x, sum_y, sum_xy, count = float(t[0]), float(t[1]), float(t[2]), int(t[3])
+    if count == 0:
+        return float("-inf")
+    if function == COVARSAMP:
+        if count - 1 == 0:
+            return float("-inf")
+        return (sum_xy / float(count - 1)) - (sum_x * sum_y) / float(count * (count - 1))
+    return (sum_xy / float(count)) - (sum_x * sum_y) / float(count * count)
+
+
+def covariance_serialize(t) -> bytes:
+    """CovarianceTuple.toBytes: double sumX, double sumY, double sumXY, long count, big-endian, 32 bytes."""
+    return struct.pack(">dddq", float(t[0]), float(t[1]), float(t[2]), int(t[3]))
+
+
 def _double_compare_key(x) -> int:
     """An int whose order is Double.compare's (NaN largest, -0.0 < 0.0)."""
     x = float(x)
@@ -205,6 +230,8 @@ def merge_intermediate(function: str, a, b):
         return a.merge(b)
     if function in VARIANCE_AGGREGATIONS:
         return variance_merge(a, b)
+    if function in COVARIANCE_AGGREGATIONS:
+        return covariance_merge(a, b)
     return np.maximum(a, b)  # HyperLogLog.addAll
 
 
@@ -228,6 +255,8 @@ def final_value(spec, value):
         return percentile_final(value, spec.percentile)
     if spec.function in VARIANCE_AGGREGATIONS:
         return variance_final(value, spec.function)
+    if spec.function in COVARIANCE_AGGREGATIONS:
+        return covariance_final(value, spec.function)
     return float(value)
 
 
