@@ -236,7 +236,46 @@ typedef struct {
  *   - a call in which a segment could reach num_groups_limit (min(product of the group-by cardinalities, docs) >= the
  *     limit);
  *   - key spaces beyond 2^40 keys or the dense table budget (8 + 64 bytes x distinct pairs per key over 32 GB);
- *   - more than 4 distinct ordered pairs. */
+ *   - more than 4 distinct ordered pairs.
+ *
+ * PH_AGG_SKEWNESS / PH_AGG_KURTOSIS: the reference's FourthMomentAggregationFunction over a pinned single-value INT,
+ * LONG, FLOAT or DOUBLE column (a raw column too).  The intermediate result of a row is the reference's
+ * PinotFourthMoment of the row's `n` matched docs: 40 bytes in host order, {int64 n; double m1; double m2; double m3;
+ * double m4} with m1 the mean and m_k = sum((x - mean)^k); a row with no doc holds (0, NaN, NaN, NaN, NaN) (commons-math's
+ * FourthMoment() leaves the moments NaN), which only an aggregation-only query that matched nothing returns.  The two
+ * functions over one column return the same tuple and differ in the final result (commons-math's Skewness / Kurtosis
+ * over the moment: with v = m2 / (n - 1), skewness is NaN for n < 3, 0.0 when v < 10E-20, else n m3 / ((n - 1)(n - 2)
+ * sqrt(v) v); kurtosis is NaN for n <= 3, 0.0 when v < 10E-20, else (n (n + 1) m4 - 3 m2^2 (n - 1)) / ((n - 1)(n - 2)
+ * (n - 3) v^2)) and in the result column name, `skewness(col)` / `kurtosis(col)`.  The reference updates the moment per
+ * doc; here the scan adds n and the power sums S_k = sum(d^k), k = 1..4, of d = x - K, K a shift of the call taken from
+ * the first and last dictionary entries of the column in the queried segments, with r the column's range over them:
+ *   - a column stored as INT or LONG with r < 2^32, in a call whose segments hold at most 2^32 docs (every INT column):
+ *     K is the smallest value, so d is unsigned, and each d^k is split into 32-bit limbs that are added into 64-bit
+ *     cells of their own (4 cells when r < 2^8, 6 when r < 2^16, else 10), which cannot overflow.  The finish
+ *     reassembles the sums, forms n K + S1, n S2 - S1^2, n^2 S3 - 3 n S1 S2 + 2 S1^3 and n^3 S4 - 4 n^2 S1 S3 +
+ *     6 n S1^2 S2 - 3 S1^4 exactly, rounds each once to double and divides by (double) n 1, 1, 2 and 3 times: m_k has at
+ *     most k + 1 roundings, m2 = m3 = m4 = 0.0 exactly when all values are equal, and the tuple is independent of the
+ *     order of the docs and bit-reproducible;
+ *   - FLOAT / DOUBLE columns, and integer columns past those bounds: K is the midpoint as a double and the four sums
+ *     are added in double (order-dependent, as a DOUBLE SUM: within 1e-9 relative of the sum of the magnitudes of the
+ *     terms of the same formulas, evaluated in doubles); m2 and m4 are clamped at 0.
+ * Served: queries whose aggregations are all of this family or COUNT(*), with or without a WHERE clause and a GROUP BY,
+ * any number of such aggregations over at most 4 distinct columns.  log2m, column2 and percentile are ignored.
+ * ph_exec_stats.scan_kernel is PH_KERNEL_SCAN_MOMENTS4; plan_mode 1 / 2 / 3.  num_docs_scanned is the matched docs,
+ * num_entries_scanned_in_filter the WHERE clause's ordinary statistic, num_entries_scanned_post_filter the matched docs
+ * x (group-by columns + distinct argument columns).  Never answered from a star-tree or from metadata.  Shapes that
+ * return PH_ERR_UNSUPPORTED, each with its own message (the CPU plan serves them):
+ *   - a STRING column, a sketch column or a non-NONE expr_op (an expression argument);
+ *   - any other aggregation beside a function of the family: SUM / MIN / MAX / DISTINCTCOUNTHLL / DISTINCTCOUNT /
+ *     PERCENTILE, the variance family and the covariance family;
+ *   - a FILTER clause on or beside one;
+ *   - multi-device contexts and the dense-partial entry points;
+ *   - segment group trim (min_segment_group_trim_size > 0 with ORDER BY);
+ *   - a call in which a segment could reach num_groups_limit (min(product of the group-by cardinalities, docs) >= the
+ *     limit);
+ *   - key spaces beyond 2^40 keys or the dense table budget (8 bytes, plus 8 per cell and a 40-byte tuple per distinct
+ *     column, per key over 32 GB);
+ *   - more than 4 distinct argument columns. */
 typedef enum {
   PH_AGG_COUNT = 0,
   PH_AGG_SUM = 1,
@@ -250,7 +289,9 @@ typedef enum {
   PH_AGG_STDDEVPOP = 9,
   PH_AGG_STDDEVSAMP = 10,
   PH_AGG_COVARPOP = 11,
-  PH_AGG_COVARSAMP = 12
+  PH_AGG_COVARSAMP = 12,
+  PH_AGG_SKEWNESS = 13,
+  PH_AGG_KURTOSIS = 14
 } ph_aggregation_type;
 
 /* 2-operand expression argument of SUM / MIN / MAX: `column <op> column2`, evaluated per row like the reference's
@@ -400,8 +441,10 @@ enum {
                                        in one pass over the group-by and value columns (plan_mode 1, 2 or 3) */
   PH_KERNEL_SCAN_MOMENTS = 21,      /* k_scan_moments<MODE, FORM> + k_moments_finish: the variance family as exact shifted
                                        moments (plan_mode 1, 2 or 3 as the tables live in registers, LDS or HBM) */
-  PH_KERNEL_SCAN_COMOMENTS = 22     /* k_scan_comoments<MODE, FORM, C> + k_comoments_finish: COVAR_POP / COVAR_SAMP as
+  PH_KERNEL_SCAN_COMOMENTS = 22,    /* k_scan_comoments<MODE, FORM, C> + k_comoments_finish: COVAR_POP / COVAR_SAMP as
                                        exact shifted co-moments over a register-direct decode (plan_mode 1, 2 or 3) */
+  PH_KERNEL_SCAN_MOMENTS4 = 23      /* k_scan_moments4<MODE, LAYOUT> + k_moments4_finish: SKEWNESS / KURTOSIS as exact
+                                       shifted power sums in 32-bit limb cells (plan_mode 1, 2 or 3) */
 };
 
 /* ------------------------------------------------------------------ context */
@@ -556,7 +599,8 @@ const void* ph_result_key_data(const ph_result* r, int32_t group_by_index);
  * PERCENTILE uint32[D] histogram over the aggregation's result dictionary: the matched docs of each value
  * (PERCENTILE aggregations over one column return the same histogram),
  * VARPOP / VARSAMP / STDDEVPOP / STDDEVSAMP {int64 count; double sum; double m2}, 24 bytes (see PH_AGG_VARPOP),
- * COVARPOP / COVARSAMP {double sum_x; double sum_y; double sum_xy; int64 count}, 32 bytes (see PH_AGG_COVARPOP) */
+ * COVARPOP / COVARSAMP {double sum_x; double sum_y; double sum_xy; int64 count}, 32 bytes (see PH_AGG_COVARPOP),
+ * SKEWNESS / KURTOSIS {int64 n; double m1; double m2; double m3; double m4}, 40 bytes (see PH_AGG_SKEWNESS) */
 int ph_result_aggregation(const ph_result* r, int32_t aggregation_index, void* out);
 const void* ph_result_aggregation_data(const ph_result* r, int32_t aggregation_index);
 /* DISTINCTCOUNT aggregation k.  Its result dictionary is the table dictionary of the column (ph_table_set_dictionary)

@@ -307,6 +307,12 @@ public final class GpuQuery {
         case PERCENTILE:  // exact: a histogram over the column's result dictionary (ph_result_percentile_*)
           type = PinotHipJni.AGG_PERCENTILE;
           break;
+        case SKEWNESS:  // exact shifted power sums; the row is a PinotFourthMoment (GpuResultSchema.FourthMomentColumn)
+          type = PinotHipJni.AGG_SKEWNESS;
+          break;
+        case KURTOSIS:
+          type = PinotHipJni.AGG_KURTOSIS;
+          break;
         default:
           return null;
       }

@@ -63,6 +63,9 @@ final class GpuResultSchema {
       case COVARPOP:
       case COVARSAMP:
         return new CovarianceColumn(res, k);
+      case SKEWNESS:
+      case KURTOSIS:
+        return new FourthMomentColumn(res, k);
       default:
         return null;
     }
@@ -101,6 +104,29 @@ final class GpuResultSchema {
       int at = 32 * row;
       return new org.apache.pinot.segment.local.customobject.CovarianceTuple(_rows.getDouble(at),
           _rows.getDouble(at + 8), _rows.getDouble(at + 16), _rows.getLong(at + 24));
+    }
+  }
+
+  /** SKEWNESS / KURTOSIS aggregation {@code k} of a result: 40-byte rows in host order, {long n; double m1; double m2;
+   *  double m3; double m4} -- the PinotFourthMoment the function's intermediate column (OBJECT) holds, rebuilt through
+   *  its own serialised form (long and four doubles, big-endian: PinotFourthMoment.fromBytes). */
+  static final class FourthMomentColumn implements RowObjects {
+    private final ByteBuffer _rows;
+
+    FourthMomentColumn(long res, int k) {
+      _rows = PinotHipJni.resultAggregationBuffer(res, k, 40).order(ByteOrder.nativeOrder());
+    }
+
+    @Override
+    public Object row(int row) {
+      int at = 40 * row;
+      ByteBuffer be = ByteBuffer.allocate(40);
+      be.putLong(_rows.getLong(at));
+      for (int i = 1; i < 5; i++) {
+        be.putDouble(_rows.getDouble(at + 8 * i));
+      }
+      be.flip();
+      return org.apache.pinot.segment.local.customobject.PinotFourthMoment.fromBytes(be);
     }
   }
 

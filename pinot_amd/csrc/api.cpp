@@ -346,6 +346,12 @@ int ph_query_execute(ph_ctx* ctx, const ph_query* query, ph_segment* const* segm
       if (query->min_segment_group_trim_size > 0 && query->num_group_by > 0 && query->num_order_by > 0)
         fail(PH_ERR_UNSUPPORTED, std::string(fn) + " with segment group trim (minSegmentGroupTrimSize)");
     }
+    if (has_moment4_aggregation(query)) {  // their own plan (moments4.cpp): exact shifted power sums in limb cells
+      moments4_validate(query);
+      if (ctx->devs.size() > 1) fail(PH_ERR_UNSUPPORTED, "fourth-moment functions on a multi-device context");
+      *out = moments4_execute(&ctx->c, query, segments, num_segments);
+      return;
+    }
     if (has_comoment_aggregation(query)) {  // their own plan (comoments.cpp): exact shifted co-moments
       comoments_validate(query);
       if (ctx->devs.size() > 1) fail(PH_ERR_UNSUPPORTED, "covariance functions on a multi-device context");
@@ -448,6 +454,10 @@ static Context* dense_device(ph_ctx* ctx, ph_segment* const* segs, int32_t n) {
 }
 
 static void reject_dense_shapes(const ph_query* q) {
+  if (has_moment4_aggregation(q)) {
+    moments4_validate(q);
+    fail(PH_ERR_UNSUPPORTED, "fourth-moment functions on dense partials");
+  }
   if (has_comoment_aggregation(q)) {
     comoments_validate(q);
     fail(PH_ERR_UNSUPPORTED, "covariance functions on dense partials");

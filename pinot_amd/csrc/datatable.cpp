@@ -130,8 +130,9 @@ std::string agg_column_name(const ph_aggregation& a) {
   // (the variance family: getType().getName().toLowerCase(), BaseSingleInputAggregationFunction.java:43-45 over
   // AggregationFunctionType.java:174-181)
   static const char* fn[] = {"count", "sum", "min", "max", "distinctcounthll", "distinctcount", "percentile",
-                             "varpop", "varsamp", "stddevpop", "stddevsamp", "covarpop", "covarsamp"};
-  if (a.type < 0 || a.type > PH_AGG_COVARSAMP) fail(PH_ERR_INVALID_ARGUMENT, "unknown aggregation");
+                             "varpop", "varsamp", "stddevpop", "stddevsamp", "covarpop", "covarsamp",
+                             "skewness", "kurtosis"};
+  if (a.type < 0 || a.type > PH_AGG_KURTOSIS) fail(PH_ERR_INVALID_ARGUMENT, "unknown aggregation");
   if (a.type == PH_AGG_COUNT) return "count(*)";
   if (a.type == PH_AGG_COVARPOP || a.type == PH_AGG_COVARSAMP)  // CovarianceAggregationFunction.getResultColumnName
     return std::string(fn[a.type]) + "(" + (a.column ? a.column : "") + "," + (a.column2 ? a.column2 : "") + ")";  // (:72-74)
@@ -256,6 +257,15 @@ std::vector<uint8_t> result_to_datatable(const ph_result* r, const ph_query* q, 
         put_be(dst, (uint32_t)var.b.size(), 4);
         put_be(dst + 4, 32u, 4);
         var.i32(32);
+        for (uint64_t x : f) var.i64((int64_t)x);
+      } else if (t == PH_AGG_SKEWNESS || t == PH_AGG_KURTOSIS) {
+        // PinotFourthMoment.serialize (PinotFourthMoment.java:107-115) as ObjectType.PinotFourthMoment
+        // (ObjectSerDeUtils.java:138): long n, double m1, m2, m3, m4, big-endian
+        uint64_t f[5];
+        memcpy(f, base + (size_t)g * 40, 40);
+        put_be(dst, (uint32_t)var.b.size(), 4);
+        put_be(dst + 4, 40u, 4);
+        var.i32(34);
         for (uint64_t x : f) var.i64((int64_t)x);
       } else if (t == PH_AGG_PERCENTILE) {
         // the DoubleArrayList of the matched values (ObjectSerDeUtils.java:328-357): int objectType 3, int size, the

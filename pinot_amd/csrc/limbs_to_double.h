@@ -1,15 +1,17 @@
 // limbs_to_double.h -- one correctly rounded conversion of a multi-limb integer to double, shared by the finish kernels
-// of the exact integer moments (scan_moments.hip, scan_comoments.hip).
+// of the exact integer moments (scan_moments.hip, scan_comoments.hip, scan_moments4.hip).
 #pragma once
 #include "scan_kernel.h"
 
 namespace ph {
 
-// a 256-bit unsigned integer (four 64-bit limbs, x[0] lowest) to double, round-to-nearest-even
-__device__ __forceinline__ double m_limbs_to_double(const unsigned long long (&x)[4]) {
+// an unsigned integer of N 64-bit limbs (x[0] lowest; four in the variance and covariance finishes, five in the fourth
+// moments') to double, round-to-nearest-even
+template <int N>
+__device__ __forceinline__ double m_limbs_to_double(const unsigned long long (&x)[N]) {
   int top = -1;
 #pragma unroll
-  for (int i = 0; i < 4; ++i)
+  for (int i = 0; i < N; ++i)
     if (x[i]) top = 64 * i + 63 - __clzll((long long)x[i]);
   if (top < 53) return (double)x[0];  // (exact; also the zero)
   const int shift = top - 52;         // the mantissa is bits [shift, shift + 53)
@@ -17,7 +19,7 @@ __device__ __forceinline__ double m_limbs_to_double(const unsigned long long (&x
   const int li = shift >> 6, off = shift & 63;
   unsigned long long a = 0ull, b = 0ull, below = 0ull;
 #pragma unroll
-  for (int k = 0; k < 4; ++k) {
+  for (int k = 0; k < N; ++k) {
     if (k == li) a = x[k];
     if (k == li + 1) b = x[k];
     if (k < li) below |= x[k];
@@ -31,7 +33,7 @@ __device__ __forceinline__ double m_limbs_to_double(const unsigned long long (&x
   } else {  // the round bit is the top bit of limb li - 1 (li >= 1 here: shift >= 64)
     unsigned long long prev = 0ull, lower = 0ull;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
+    for (int k = 0; k < N; ++k) {
       if (k == li - 1) prev = x[k];
       if (k < li - 1) lower |= x[k];
     }

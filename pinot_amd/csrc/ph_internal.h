@@ -561,6 +561,53 @@ size_t comoments_lds_bytes(const CParams& p, int mode, int form);
 void launch_scan_comoments(const CParams& p, int mode, int form, int max_bits, int grid, hipStream_t s);
 void launch_comoments_finish(const CFinishParams& p, hipStream_t s);
 
+// Fourth moments (scan_moments4.hip, moments4.cpp): SKEWNESS / KURTOSIS.  A slot is one argument column; per group it
+// accumulates the power sums S1..S4 of d = value - K beside the docs n of the group.  In the integer layouts K is the
+// column's smallest value over the call's segments, so d is unsigned, and every power d^k is split into 32-bit limbs,
+// each added into a 64-bit cell of its own: a limb is below 2^32 and a call holds at most 2^32 docs, so no cell
+// overflows, no add returns a value and nothing carries before k_moments4_finish.  The layout follows the range r of
+// the column over the call (the cells of S1, S2, S3, S4):
+constexpr int kM4MaxCells = 10;
+enum : int32_t {
+  M4_L8 = 0,    // r < 2^8:  d^4 < 2^32, 1 + 1 + 1 + 1 cells
+  M4_L16 = 1,   // r < 2^16: d^2 < 2^32, d^3 < 2^48, d^4 < 2^64: 1 + 1 + 2 + 2 cells
+  M4_L32 = 2,   // r < 2^32: 1 + 2 + 3 + 4 cells
+  M4_REAL = 3,  // d = (double) value - K (K the midpoint), four f64 cells
+};
+constexpr int m4_cells(int layout) { return layout == M4_L32 ? 10 : (layout == M4_L16 ? 6 : 4); }
+// the segments are the variance plan's MSegment (d_of[dictId]: d as a u64, or the bits of the double d in M4_REAL)
+struct M4Params {
+  const MSegment* segs;
+  const Chunk* chunks;
+  int32_t chunk_begin, chunk_end;
+  int32_t num_slots, num_group_cols;
+  int32_t slot_col[kMMaxSlots];                   // the MSegment column (vfwd / d_of index) of this launch's slot s
+  int64_t group_stride[kMaxGroupCols];
+  int64_t num_groups;                             // dense key space (1 without a group-by)
+  // zeroed tables; n [num_groups] and seg_count (docs per segment) are nullptr in a call's later launches (the slots of
+  // another layout over the same docs), which then count nothing
+  unsigned long long* n;
+  unsigned long long* cells[kMMaxSlots];          // slot s: m4_cells(layout) tables of [num_groups], one after the other
+  unsigned long long* seg_count;
+};
+// k_moments4_finish: one thread per (group, slot) turns (n, the cells) into the reference's PinotFourthMoment
+struct M4Tuple {
+  int64_t n;
+  double m1, m2, m3, m4;
+};
+struct M4FinishParams {
+  int64_t num_groups;
+  int32_t num_slots;
+  int32_t layout[kMMaxSlots];
+  int64_t shift[kMMaxSlots];                      // K: an int64, or a double's bits (M4_REAL)
+  const unsigned long long* n;
+  const unsigned long long* cells[kMMaxSlots];
+  M4Tuple* out[kMMaxSlots];                       // [num_groups]
+};
+size_t moments4_lds_bytes(const M4Params& p, int mode, int layout);
+void launch_scan_moments4(const M4Params& p, int mode, int layout, int grid, hipStream_t s);
+void launch_moments4_finish(const M4FinishParams& p, hipStream_t s);
+
 // Kernel B of the partitioned group-by: aggregates one batch of records per partition in LDS, then merges
 // the partition's key range into the dense result table (each key range has exactly one owner block).
 struct PartAggParams {
@@ -1218,6 +1265,10 @@ ph_result* moments_execute(Context* ctx, const ph_query* q, ph_segment* const* s
 bool has_comoment_aggregation(const ph_query* q);
 void comoments_validate(const ph_query* q);  // host-only argument and shape checks of such a query
 ph_result* comoments_execute(Context* ctx, const ph_query* q, ph_segment* const* segs, int32_t nseg);
+// fourth moments (moments4.cpp): a SKEWNESS / KURTOSIS somewhere in the query
+bool has_moment4_aggregation(const ph_query* q);
+void moments4_validate(const ph_query* q);  // host-only argument and shape checks of such a query
+ph_result* moments4_execute(Context* ctx, const ph_query* q, ph_segment* const* segs, int32_t nseg);
 // FilterContext.toString of the tree rooted at `root` (FilterContext.java:94-114 and each Predicate.toString)
 std::string filter_to_string(const ph_query* q, int32_t root);
 ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const* segs, int32_t nseg,

@@ -7,7 +7,8 @@ dictionary, DataSchema.fromBytes, fixed-size rows, variable-size data, metadata 
 GroupByDataTableReducer.reduceAndSetResults (core/query/reduce/GroupByDataTableReducer.java:99) /
 AggregationDataTableReducer -- intermediate results merged per group key with AggregationFunction.merge
 (COUNT / SUM add, MIN / MAX, DISTINCTCOUNTHLL HyperLogLog.addAll = register max, DISTINCTCOUNT set union, PERCENTILE
-DoubleArrayList.addAll, the variance family VarianceTuple.apply, COVARPOP / COVARSAMP CovarianceTuple.apply), then the final results, ORDER BY
+DoubleArrayList.addAll, the variance family VarianceTuple.apply, COVARPOP / COVARSAMP CovarianceTuple.apply,
+SKEWNESS / KURTOSIS PinotFourthMoment.combine), then the final results, ORDER BY
 and LIMIT (pinot_amd.reduce.reduce_groups).
 """
 from __future__ import annotations
@@ -18,8 +19,8 @@ from typing import Any, Dict, List, Sequence
 
 import numpy as np
 
-from .query import (COUNT, COVARIANCE_AGGREGATIONS, DISTINCTCOUNT, DISTINCTCOUNTHLL, MAX, MIN, PERCENTILE, SUM,
-                    VARIANCE_AGGREGATIONS, QueryContext)
+from .query import (COUNT, COVARIANCE_AGGREGATIONS, DISTINCTCOUNT, DISTINCTCOUNTHLL, FOURTHMOMENT_AGGREGATIONS, MAX, MIN,
+                    PERCENTILE, SUM, VARIANCE_AGGREGATIONS, QueryContext)
 from .reduce import ResultTable, ValueCounts, merge_intermediate, reduce_groups
 
 # MetadataKey id -> (name, value type) (DataTable.java:103-137); "I" int, "L" long, "S" string
@@ -43,6 +44,7 @@ SET_OBJECT_TYPES = {9: "INT", 15: "LONG", 16: "FLOAT", 17: "DOUBLE", 18: "STRING
 DOUBLE_LIST_OBJECT_TYPE = 3  # ObjectSerDeUtils.ObjectType.DoubleArrayList: PERCENTILE's matched values
 VARIANCE_TUPLE_OBJECT_TYPE = 33  # ObjectSerDeUtils.ObjectType.VarianceTuple (ObjectSerDeUtils.java:137)
 COVARIANCE_TUPLE_OBJECT_TYPE = 32  # ObjectSerDeUtils.ObjectType.CovarianceTuple (ObjectSerDeUtils.java:136)
+FOURTHMOMENT_OBJECT_TYPE = 34  # ObjectSerDeUtils.ObjectType.PinotFourthMoment (ObjectSerDeUtils.java:138)
 
 
 @dataclass
@@ -141,6 +143,13 @@ def covariance_deserialize(b: bytes) -> tuple:
     if len(b) != 32:
         raise ValueError(f"CovarianceTuple of {len(b)} bytes")
     return struct.unpack(">dddq", b)
+
+
+def fourthmoment_deserialize(b: bytes) -> tuple:
+    """An (n, m1, m2, m3, m4) tuple from PinotFourthMoment.serialize (:107-115): long, four doubles, big-endian."""
+    if len(b) != 40:
+        raise ValueError(f"PinotFourthMoment of {len(b)} bytes")
+    return struct.unpack(">qdddd", b)
 
 
 def decode(buf: bytes) -> DataTable:
@@ -242,6 +251,10 @@ def reduce_datatables(q: QueryContext, tables: Sequence[DataTable]) -> ResultTab
                     otype, payload = v
                     assert otype == COVARIANCE_TUPLE_OBJECT_TYPE
                     v = covariance_deserialize(payload)
+                elif a.function in FOURTHMOMENT_AGGREGATIONS:
+                    otype, payload = v
+                    assert otype == FOURTHMOMENT_OBJECT_TYPE
+                    v = fourthmoment_deserialize(payload)
                 inter.append(v)
             if key in groups:
                 groups[key] = [_merge(a.function, x, y) for a, x, y in zip(q.aggregations, groups[key], inter)]
@@ -250,6 +263,7 @@ def reduce_datatables(q: QueryContext, tables: Sequence[DataTable]) -> ResultTab
     if not nk and not groups:
         empty = {f: (0, 0.0, 0.0) for f in VARIANCE_AGGREGATIONS}
         empty.update({f: (0.0, 0.0, 0.0, 0) for f in COVARIANCE_AGGREGATIONS}, COUNT=0)
+        empty.update({f: (0,) + (float("nan"),) * 4 for f in FOURTHMOMENT_AGGREGATIONS})
         groups[()] = [empty.get(a.function) for a in q.aggregations]
     keys = list(groups)
     return reduce_groups(q, keys, [groups[k] for k in keys])

@@ -18,9 +18,9 @@ from typing import List, Sequence
 import numpy as np
 
 from . import native as N
-from .query import (COUNT, COVARIANCE_AGGREGATIONS, COVARPOP, COVARSAMP, DISTINCTCOUNT, DISTINCTCOUNTHLL, MAX, MIN,
-                    PERCENTILE, STDDEVPOP, STDDEVSAMP, SUM, VARIANCE_AGGREGATIONS, VARPOP, VARSAMP, FilterContext,
-                    QueryContext, parse_sql)
+from .query import (COUNT, COVARIANCE_AGGREGATIONS, COVARPOP, COVARSAMP, DISTINCTCOUNT, DISTINCTCOUNTHLL,
+                    FOURTHMOMENT_AGGREGATIONS, KURTOSIS, MAX, MIN, PERCENTILE, SKEWNESS, STDDEVPOP, STDDEVSAMP, SUM,
+                    VARIANCE_AGGREGATIONS, VARPOP, VARSAMP, FilterContext, QueryContext, parse_sql)
 from .reduce import ResultTable, ValueCounts, reduce_groups
 from .segment import PinnedSegment, SegmentBuffers
 
@@ -28,7 +28,7 @@ _AGG = {COUNT: N.PH_AGG_COUNT, SUM: N.PH_AGG_SUM, MIN: N.PH_AGG_MIN, MAX: N.PH_A
         DISTINCTCOUNTHLL: N.PH_AGG_DISTINCTCOUNTHLL, DISTINCTCOUNT: N.PH_AGG_DISTINCTCOUNT,
         PERCENTILE: N.PH_AGG_PERCENTILE, VARPOP: N.PH_AGG_VARPOP, VARSAMP: N.PH_AGG_VARSAMP,
         STDDEVPOP: N.PH_AGG_STDDEVPOP, STDDEVSAMP: N.PH_AGG_STDDEVSAMP, COVARPOP: N.PH_AGG_COVARPOP,
-        COVARSAMP: N.PH_AGG_COVARSAMP}
+        COVARSAMP: N.PH_AGG_COVARSAMP, SKEWNESS: N.PH_AGG_SKEWNESS, KURTOSIS: N.PH_AGG_KURTOSIS}
 _PRED = {"EQ": N.PH_PRED_EQ, "NOT_EQ": N.PH_PRED_NOT_EQ, "IN": N.PH_PRED_IN, "NOT_IN": N.PH_PRED_NOT_IN,
          "RANGE": N.PH_PRED_RANGE}
 
@@ -64,7 +64,7 @@ SCAN_KERNEL_NAMES = {0: "none", 1: "k_scan", 2: "k_agg_lean", 3: "k_agg_sparse",
                      16: "k_scan, DISTINCTCOUNT bitsets in LDS", 17: "k_scan, DISTINCTCOUNT bitsets in HBM",
                      18: "k_scan, PERCENTILE histograms in LDS", 19: "k_scan, PERCENTILE histograms in HBM",
                      20: "k_scan_filtered", 21: "k_scan_moments + k_moments_finish",
-                     22: "k_scan_comoments + k_comoments_finish"}
+                     22: "k_scan_comoments + k_comoments_finish", 23: "k_scan_moments4 + k_moments4_finish"}
 
 
 @dataclass
@@ -110,7 +110,7 @@ class IntermediateResult:
     key_columns: List[object]   # per group-by column: numpy array (numeric) or list of str
     # per aggregation: int64 (COUNT), float64 (SUM/MIN/MAX), uint8[n, m] (HLL), DistinctColumn (DISTINCTCOUNT),
     # HistogramColumn (PERCENTILE), VARIANCE_TUPLE_DTYPE records (VARPOP / VARSAMP / STDDEVPOP / STDDEVSAMP),
-    # COVARIANCE_TUPLE_DTYPE records (COVARPOP / COVARSAMP)
+    # COVARIANCE_TUPLE_DTYPE records (COVARPOP / COVARSAMP), FOURTHMOMENT_TUPLE_DTYPE records (SKEWNESS / KURTOSIS)
     agg_columns: List[object]
     num_groups: int
     functions: List[str]
@@ -136,7 +136,8 @@ class IntermediateResult:
                 conv.append([col.value_set(i) for i in range(self.num_groups)])
             elif f == PERCENTILE:  # value multisets: partial results of different calls merge by value
                 conv.append([col.value_counts(i) for i in range(self.num_groups)])
-            elif f in VARIANCE_AGGREGATIONS + COVARIANCE_AGGREGATIONS:  # (count, sum, m2) / (sum_x, sum_y, sum_xy, count)
+            elif f in VARIANCE_AGGREGATIONS + COVARIANCE_AGGREGATIONS + FOURTHMOMENT_AGGREGATIONS:
+                # (count, sum, m2) / (sum_x, sum_y, sum_xy, count) / (n, m1, m2, m3, m4)
                 conv.append([tuple(t) for t in col.tolist()])
             else:
                 conv.append(col.tolist())
@@ -244,6 +245,9 @@ VARIANCE_TUPLE_DTYPE = np.dtype([("count", np.int64), ("sum", np.float64), ("m2"
 # a covariance function's result row: the reference's CovarianceTuple in host order
 COVARIANCE_TUPLE_DTYPE = np.dtype([("sum_x", np.float64), ("sum_y", np.float64), ("sum_xy", np.float64),
                                    ("count", np.int64)])
+# a SKEWNESS / KURTOSIS result row: the reference's PinotFourthMoment in host order
+FOURTHMOMENT_TUPLE_DTYPE = np.dtype([("n", np.int64), ("m1", np.float64), ("m2", np.float64), ("m3", np.float64),
+                                     ("m4", np.float64)])
 _KEY_DTYPE = {N.PH_INT: np.int32, N.PH_LONG: np.int64, N.PH_FLOAT: np.float32, N.PH_DOUBLE: np.float64}
 
 
@@ -472,6 +476,8 @@ class GpuContext:
                 arr = view(L.ph_result_aggregation_data(r, k), 24 * n).view(VARIANCE_TUPLE_DTYPE)
             elif a.function in COVARIANCE_AGGREGATIONS:
                 arr = view(L.ph_result_aggregation_data(r, k), 32 * n).view(COVARIANCE_TUPLE_DTYPE)
+            elif a.function in FOURTHMOMENT_AGGREGATIONS:
+                arr = view(L.ph_result_aggregation_data(r, k), 40 * n).view(FOURTHMOMENT_TUPLE_DTYPE)
             elif a.function == COUNT:
                 arr = view(L.ph_result_aggregation_data(r, k), 8 * n).view(np.int64)
             else:

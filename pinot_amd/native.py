@@ -26,7 +26,7 @@ PH_PRED_EQ, PH_PRED_NOT_EQ, PH_PRED_IN, PH_PRED_NOT_IN, PH_PRED_RANGE = range(5)
 PH_FILTER_AND, PH_FILTER_OR, PH_FILTER_NOT, PH_FILTER_PREDICATE = range(4)
 (PH_AGG_COUNT, PH_AGG_SUM, PH_AGG_MIN, PH_AGG_MAX, PH_AGG_DISTINCTCOUNTHLL, PH_AGG_DISTINCTCOUNT,
  PH_AGG_PERCENTILE, PH_AGG_VARPOP, PH_AGG_VARSAMP, PH_AGG_STDDEVPOP, PH_AGG_STDDEVSAMP, PH_AGG_COVARPOP,
- PH_AGG_COVARSAMP) = range(13)
+ PH_AGG_COVARSAMP, PH_AGG_SKEWNESS, PH_AGG_KURTOSIS) = range(15)
 
 
 class PinotHipError(RuntimeError):
@@ -101,6 +101,7 @@ class FilteredAggregation(ctypes.Structure):
 PH_KERNEL_SCAN_FILTERED = 20
 PH_KERNEL_SCAN_MOMENTS = 21
 PH_KERNEL_SCAN_COMOMENTS = 22
+PH_KERNEL_SCAN_MOMENTS4 = 23
 
 
 class OrderBy(ctypes.Structure):

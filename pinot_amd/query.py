@@ -36,8 +36,12 @@ VARIANCE_AGGREGATIONS = (VARPOP, VARSAMP, STDDEVPOP, STDDEVSAMP)
 # count) per result holder
 COVARPOP, COVARSAMP = "COVARPOP", "COVARSAMP"
 COVARIANCE_AGGREGATIONS = (COVARPOP, COVARSAMP)
+# SKEWNESS(x) / KURTOSIS(x) (FourthMomentAggregationFunction.java): a PinotFourthMoment (n, m1, m2, m3, m4) per result
+# holder; FOURTHMOMENT itself has no final result there (:165-168) and stays an unsupported function
+SKEWNESS, KURTOSIS = "SKEWNESS", "KURTOSIS"
+FOURTHMOMENT_AGGREGATIONS = (SKEWNESS, KURTOSIS)
 SUPPORTED_AGGREGATIONS = ((COUNT, SUM, MIN, MAX, DISTINCTCOUNTHLL, DISTINCTCOUNT, PERCENTILE) + VARIANCE_AGGREGATIONS
-                          + COVARIANCE_AGGREGATIONS)
+                          + COVARIANCE_AGGREGATIONS + FOURTHMOMENT_AGGREGATIONS)
 DEFAULT_HLL_LOG2M = 8  # CommonConstants.Helix.DEFAULT_HYPERLOGLOG_LOG2M (CommonConstants.java:96-97)
 DEFAULT_NUM_GROUPS_LIMIT = 100_000  # InstancePlanMakerImplV2.DEFAULT_NUM_GROUPS_LIMIT (:72-73)
 DEFAULT_QUERY_LIMIT = 10
@@ -370,7 +374,7 @@ class _Parser:
         # (AggregationFunctionType.getNormalizedAggregationFunctionName, AggregationFunctionType.java:424-426), so
         # VAR_POP, varPop and stddev_samp; the result column name is the type's name in lower case,
         # `varpop(col)` (BaseSingleInputAggregationFunction.getResultColumnName :43-45), which result_name gives
-        if fn.replace("_", "") in VARIANCE_AGGREGATIONS + COVARIANCE_AGGREGATIONS:
+        if fn.replace("_", "") in VARIANCE_AGGREGATIONS + COVARIANCE_AGGREGATIONS + FOURTHMOMENT_AGGREGATIONS:
             fn = fn.replace("_", "")
         if t[0] == "id" and n == ("op", "(") and fn in SUPPORTED_AGGREGATIONS:
             self.i += 2
@@ -397,7 +401,7 @@ class _Parser:
                 if not (self.peek() == ("op", ")")):
                     raise SqlParseError(f"{fn} takes two column arguments")
             elif self.accept("op", ","):
-                if fn == DISTINCTCOUNT or fn in VARIANCE_AGGREGATIONS:
+                if fn == DISTINCTCOUNT or fn in VARIANCE_AGGREGATIONS + FOURTHMOMENT_AGGREGATIONS:
                     raise SqlParseError(f"{fn} takes one argument")
                 log2m = int(self.literal())
             self.expect("op", ")")

@@ -9,7 +9,9 @@ Mirrors the final steps the reference applies after the server-side combine:
   VARPOP / VARSAMP / STDDEVPOP / STDDEVSAMP -> m2 / count or m2 / (count - 1), its square root for STDDEV
   (VarianceAggregationFunction.java:228-248),
   COVARPOP / COVARSAMP -> sumXY / count - sumX sumY / (count count), or its sample form
-  (CovarianceAggregationFunction.java:185-201).
+  (CovarianceAggregationFunction.java:185-201),
+  SKEWNESS / KURTOSIS -> commons-math 3's Skewness / Kurtosis over the merged PinotFourthMoment (restated from their
+  published form: parity unpinned).
 * ``IndexedTable.finish`` / ``GroupByDataTableReducer.reduceAndSetResults`` -- ORDER BY over group-by
   columns and aggregations (ASC/DESC), then LIMIT (core/data/table/IndexedTable.java:148-173,
   core/query/reduce/GroupByDataTableReducer.java:99).
@@ -27,8 +29,9 @@ from typing import Any, List, Sequence
 
 import numpy as np
 
-from .query import (COUNT, COVARIANCE_AGGREGATIONS, COVARSAMP, DISTINCTCOUNT, DISTINCTCOUNTHLL, MAX, MIN, PERCENTILE,
-                    STDDEVPOP, STDDEVSAMP, SUM, VARIANCE_AGGREGATIONS, VARSAMP, QueryContext)
+from .query import (COUNT, COVARIANCE_AGGREGATIONS, COVARSAMP, DISTINCTCOUNT, DISTINCTCOUNTHLL,
+                    FOURTHMOMENT_AGGREGATIONS, MAX, MIN, PERCENTILE, SKEWNESS, STDDEVPOP, STDDEVSAMP, SUM,
+                    VARIANCE_AGGREGATIONS, VARSAMP, QueryContext)
 
 
 def _java_round(x: float) -> int:
@@ -189,6 +192,52 @@ def covariance_serialize(t) -> bytes:
     return struct.pack(">dddq", float(t[0]), float(t[1]), float(t[2]), int(t[3]))
 
 
+def fourthmoment_merge(a, b) -> tuple:
+    """PinotFourthMoment.combine (PinotFourthMoment.java:55-97) on (n, m1, m2, m3, m4) tuples, in its order of
+    operations (Java multiplies a double by a long in double, left to right; n * n is a long product)."""
+    an, am1, am2, am3, am4 = int(a[0]), float(a[1]), float(a[2]), float(a[3]), float(a[4])
+    bn, bm1, bm2, bm3, bm4 = int(b[0]), float(b[1]), float(b[2]), float(b[3]), float(b[4])
+    if bn == 0:
+        return (an, am1, am2, am3, am4)
+    if an == 0:
+        return (bn, bm1, bm2, bm3, bm4)
+    n = an + bn
+    fa, fb, fn = float(an), float(bn), float(n)
+    m1 = (fa * am1 + fb * bm1) / fn
+    delta = bm1 - am1
+    delta2 = delta * delta
+    m2 = am2 + bm2 + delta2 * fa * fb / fn
+    delta3 = delta2 * delta
+    m3 = am3 + bm3 + delta3 * fa * fb * float(an - bn) / float(n * n) + 3.0 * delta * (fa * bm2 - fb * am2) / fn
+    delta4 = delta3 * delta
+    n3 = fn * fn * fn
+    m4 = (am4 + bm4 + delta4 * fa * fb * float(an * an - an * bn + bn * bn) / n3
+          + 6.0 * delta2 * (float(an * an) * bm2 + float(bn * bn) * am2) / float(n * n)
+          + 4.0 * delta * (fa * bm3 - fb * am3) / fn)
+    return (n, m1, m2, m3, m4)
+
+
+def fourthmoment_final(t, function: str) -> float:
+    """commons-math 3's Skewness.getResult / Kurtosis.getResult over the moment, restated from their published form:
+    with v = m2 / (n - 1), skewness is NaN for n < 3, 0.0 when v < 10E-20, else n m3 / ((n - 1)(n - 2) sqrt(v) v);
+    kurtosis is NaN for n <= 3, 0.0 when v < 10E-20, else (n (n + 1) m4 - 3 m2^2 (n - 1)) / ((n - 1)(n - 2)(n - 3) v^2)."""
+    n, m2, m3, m4 = int(t[0]), float(t[2]), float(t[3]), float(t[4])
+    if n < 3 or (function != SKEWNESS and n <= 3):
+        return float("nan")
+    n0 = float(n)
+    v = m2 / (n0 - 1.0)
+    if v < 10E-20:
+        return 0.0
+    if function == SKEWNESS:
+        return (n0 * m3) / ((n0 - 1.0) * (n0 - 2.0) * math.sqrt(v) * v)
+    return (n0 * (n0 + 1.0) * m4 - 3.0 * m2 * m2 * (n0 - 1.0)) / ((n0 - 1.0) * (n0 - 2.0) * (n0 - 3.0) * v * v)
+
+
+def fourthmoment_serialize(t) -> bytes:
+    """PinotFourthMoment.serialize (:107-115): long n, double m1, m2, m3, m4, big-endian, 40 bytes."""
+    return struct.pack(">qdddd", int(t[0]), float(t[1]), float(t[2]), float(t[3]), float(t[4]))
+
+
 def _double_compare_key(x) -> int:
     """An int whose order is Double.compare's (NaN largest, -0.0 < 0.0)."""
     x = float(x)
@@ -232,6 +281,8 @@ def merge_intermediate(function: str, a, b):
         return variance_merge(a, b)
     if function in COVARIANCE_AGGREGATIONS:
         return covariance_merge(a, b)
+    if function in FOURTHMOMENT_AGGREGATIONS:
+        return fourthmoment_merge(a, b)
     return np.maximum(a, b)  # HyperLogLog.addAll
 
 
@@ -257,6 +308,8 @@ def final_value(spec, value):
         return variance_final(value, spec.function)
     if spec.function in COVARIANCE_AGGREGATIONS:
         return covariance_final(value, spec.function)
+    if spec.function in FOURTHMOMENT_AGGREGATIONS:
+        return fourthmoment_final(value, spec.function)
     return float(value)
 
 
