@@ -16,18 +16,21 @@
 //
 // Stage 1 plans every filter exactly as a WHERE clause (query_execute_impl's COUNT(*) + doc bitmap form, the one
 // ph_filter_execute drives) and leaves one doc bitmap per (segment, filter) in per-call scratch; stage 2 is one
-// k_scan_filtered launch (scan_filtered.hip) that reads the group-by and value streams once.
+// k_scan_filtered launch (scan_filtered.hip) that reads the group-by and value streams once.  The steps this plan has
+// in common with the moment plans are scan_plan.h's.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstring>
 #include <set>
 
-#include "ph_internal.h"
+#include "scan_plan.h"
 
 namespace ph {
 
 namespace {
+
+constexpr Family kFamily{"filtered", "filtered aggregations"};
 
 std::string lit(const char* s) { return s ? std::string(s) : std::string(); }
 
@@ -132,9 +135,7 @@ std::string filter_to_string(const ph_query* q, int32_t root) {
 }
 
 void filtered_validate(const ph_query* q) {
-  if (!q) fail(PH_ERR_INVALID_ARGUMENT, "null query");
-  if (q->num_aggregations < 0 || (q->num_aggregations > 0 && !q->aggregations))
-    fail(PH_ERR_INVALID_ARGUMENT, "bad aggregation list");
+  check_query(q);
   const size_t nn = (size_t)std::max(0, q->num_filter_nodes);
   std::vector<char> state(nn, 0);
   if (q->filter_root >= 0) walk_tree(q, q->filter_root, state, 0);
@@ -166,29 +167,13 @@ void filtered_validate(const ph_query* q) {
   }
   if ((int)roots.size() > kFMaxSubFilters)
     fail(PH_ERR_UNSUPPORTED, "more than " + std::to_string(kFMaxSubFilters) + " distinct FILTER clauses in one query");
-  if (q->num_aggregations > kMaxAggs) fail(PH_ERR_UNSUPPORTED, "too many aggregations");
-  if (q->num_group_by > kMaxGroupCols) fail(PH_ERR_UNSUPPORTED, "too many group-by columns");
-  if (q->min_segment_group_trim_size > 0 && q->num_group_by > 0 && q->num_order_by > 0)
-    fail(PH_ERR_UNSUPPORTED, "filtered aggregations with segment group trim (minSegmentGroupTrimSize)");
+  check_shape(kFamily, q);
 }
 
 ph_result* filtered_execute(Context* ctx, const ph_query* q, ph_segment* const* segs_in, int32_t nseg) {
-  using clock = std::chrono::steady_clock;
-  const auto t0 = clock::now();
+  const auto t0 = std::chrono::steady_clock::now();
   filtered_validate(q);
-  if (nseg < 0 || (nseg > 0 && !segs_in)) fail(PH_ERR_INVALID_ARGUMENT, "bad segment list");
-  std::vector<ph_segment*> segs(segs_in, segs_in + nseg);
-  for (auto* s : segs)
-    if (!s || s->ctx != ctx) fail(PH_ERR_INVALID_ARGUMENT, "segment is null or pinned on another context");
-  auto check_interrupt = [&]() {
-    if (q->interrupt && *q->interrupt) fail(PH_ERR_CANCELLED, "query interrupted");
-    if (q->end_time_ms > 0) {
-      const int64_t now = std::chrono::duration_cast<std::chrono::milliseconds>(
-                              std::chrono::system_clock::now().time_since_epoch()).count();
-      if (now > q->end_time_ms) fail(PH_ERR_CANCELLED, "query timed out (end time passed)");
-    }
-  };
-  check_interrupt();
+  const std::vector<ph_segment*> segs = check_call(ctx, q, segs_in, nseg);
 
   // ---- pipelines, value terms and slots
   const int nagg = q->num_aggregations;
@@ -205,11 +190,8 @@ ph_result* filtered_execute(Context* ctx, const ph_query* q, ph_segment* const* 
     agg_pipe[k] = at + 1;
   }
   const int K = (int)sub_roots.size(), P = K + 1;
-  std::vector<std::string> group_cols, val_cols;
-  for (int g = 0; g < q->num_group_by; ++g) {
-    if (!q->group_by || !q->group_by[g]) fail(PH_ERR_INVALID_ARGUMENT, "null group-by column");
-    group_cols.push_back(q->group_by[g]);
-  }
+  const std::vector<std::string> group_cols = group_columns(q);
+  std::vector<std::string> val_cols;
   std::vector<int> agg_val(nagg, -1);
   for (int k = 0; k < nagg; ++k) {
     const ph_aggregation& a = q->aggregations[k];
@@ -230,22 +212,12 @@ ph_result* filtered_execute(Context* ctx, const ph_query* q, ph_segment* const* 
   std::vector<int> val_is_int(nvals, 1), val_widened(nvals, 0);
   double docs_queried = 0.0;
   for (auto* s : segs) docs_queried += (double)s->num_docs;
-  for (auto* s : segs) {
-    for (auto& c : group_cols)
-      if (!s->columns.count(c)) fail(PH_ERR_BAD_QUERY, "Column not found: " + c + " in segment " + s->name);
-    for (int i = 0; i < q->num_predicates; ++i) {
-      if (!q->predicates[i].column) fail(PH_ERR_BAD_QUERY, "predicate without column");
-      if (!s->columns.count(q->predicates[i].column))
-        fail(PH_ERR_BAD_QUERY, std::string("Column not found: ") + q->predicates[i].column);
-    }
-  }
+  check_columns(q, segs, group_cols);
   for (int j = 0; j < nvals; ++j) {
     int col_int = -1;
     double amax = 0.0;
     for (auto* s : segs) {
-      auto it = s->columns.find(val_cols[j]);
-      if (it == s->columns.end()) fail(PH_ERR_BAD_QUERY, "Column not found: " + val_cols[j] + " in segment " + s->name);
-      const Column& c = *it->second;
+      const Column& c = column_in(s, val_cols[j]);
       if (c.data_type == PH_STRING) fail(PH_ERR_UNSUPPORTED, "numeric aggregation on STRING column " + val_cols[j]);
       if (c.sketch_words) fail(PH_ERR_UNSUPPORTED, "sketch column " + val_cols[j] + " outside DISTINCTCOUNTHLL");
       const int ci = c.data_type == PH_INT || c.data_type == PH_LONG;
@@ -298,8 +270,7 @@ ph_result* filtered_execute(Context* ctx, const ph_query* q, ph_segment* const* 
   std::vector<int32_t> main_cls(nseg, FP_ALL);
   std::vector<std::vector<int32_t>> sub_cls(nseg, std::vector<int32_t>((size_t)K, FP_ALL));
   for (int i = 0; i < nseg; ++i) {
-    if (q->filter_root >= 0) main_cls[i] = filter_plan_class(q, q->filter_root, segs[i]);
-    else if (segs[i]->num_docs == 0) main_cls[i] = FP_EMPTY;
+    main_cls[i] = where_class(q, segs[i]);
     for (int f = 0; f < K; ++f) sub_cls[i][f] = filter_plan_class(q, sub_roots[f], segs[i]);
   }
   // a CombinedFilterOperator's statistic is derived for single-leaf sub-filters only
@@ -308,46 +279,15 @@ ph_result* filtered_execute(Context* ctx, const ph_query* q, ph_segment* const* 
       if (main_cls[i] >= FP_SCAN_LEAF && sub_cls[i][f] == FP_COMPOSITE)
         fail(PH_ERR_UNSUPPORTED, "FILTER clause of several predicates (or over a legacy range index) under a WHERE clause");
 
-  // ---- key space
-  std::vector<std::shared_ptr<GlobalDict>> gdicts;
-  int64_t G = 1;
-  for (auto& g : group_cols) {
-    if (segs.empty()) fail(PH_ERR_UNSUPPORTED, "filtered group-by without segments");
-    gdicts.push_back(union_dictionary(g, segs));
-    const int64_t sz = std::max<int64_t>(1, gdicts.back()->dict.size);
-    if (G > (int64_t(1) << 40) / sz) fail(PH_ERR_UNSUPPORTED, "filtered aggregations over a group key space beyond the dense tables");
-    G *= sz;
-  }
-  const int64_t group_limit = q->num_groups_limit > 0 ? q->num_groups_limit : 100000;
-  if (!group_cols.empty())
-    for (int i = 0; i < nseg; ++i) {
-      if (main_cls[i] == FP_EMPTY) continue;
-      int64_t pp = 1;
-      for (auto& g : group_cols) {
-        const int64_t c = std::max<int64_t>(1, segs[i]->columns.at(g)->cardinality);
-        pp = pp > (int64_t(1) << 40) / c ? int64_t(1) << 40 : pp * c;
-      }
-      // past the limit the reference's group ids depend on the order of a HashMap over FilterContexts
-      if (std::min<int64_t>(pp, segs[i]->num_docs) >= group_limit)
-        fail(PH_ERR_UNSUPPORTED, "filtered aggregations where a segment could reach numGroupsLimit");
-    }
-  const double table_bytes = (double)G * 8.0 * (double)(P + ns);
-  if (table_bytes > kDenseTableBudget)
-    fail(PH_ERR_UNSUPPORTED, "filtered aggregations over a group key space beyond the dense tables");
-  int mode = MODE_AGG;
-  if (!group_cols.empty()) {
-    size_t lds_table_max = 64 * 1024;
-    if (ctx->has(OPT_LDS_TABLE_MAX)) lds_table_max = (size_t)std::max<int64_t>(0, ctx->opt(OPT_LDS_TABLE_MAX));
-    lds_table_max = std::min<size_t>(lds_table_max, 160 * 1024);
-    mode = table_bytes <= (double)lds_table_max ? MODE_GROUP_LDS : MODE_GROUP_GLOBAL;
-  }
+  // ---- key space, mode
+  const KeySpace ks = key_space(kFamily, group_cols, segs);
+  const int64_t G = ks.G;
+  refuse_group_limit(kFamily, q, ks, segs, main_cls);
+  const double table_bytes = (double)G * 8.0 * (double)(P + ns);  // a doc count per pipeline, a cell per slot
+  const int mode = choose_mode(ctx, kFamily, ks, table_bytes, table_bytes);
 
-  PH_HIP_CHECK(hipSetDevice(ctx->device));
-  auto res = std::make_unique<ph_result>();
-  res->ctx = ctx;
+  auto res = new_result(ctx, segs);
   ph_exec_stats& stats = res->stats;
-  stats.num_segments_processed = nseg;
-  for (auto* s : segs) stats.num_total_docs += s->num_docs;
   double dev_ms = 0.0;
 
   LaneGuard lane(ctx);
@@ -361,46 +301,16 @@ ph_result* filtered_execute(Context* ctx, const ph_query* q, ph_segment* const* 
   Scratch scratch(ctx, st);
 
   // ---- stage 1: one doc bitmap per (segment, filter that is neither empty nor matching all)
-  struct Bitmap {
-    unsigned long long* words = nullptr;
-    int64_t docs = 0, entries = 0;  // matched docs; the filter's ordinary numEntriesScannedInFilter
-  };
-  auto run_filter = [&](int32_t root, ph_segment* seg) {
-    Bitmap b;
-    const int64_t need = std::max<int64_t>(1, ((int64_t)seg->num_docs + 63) / 64);
-    b.words = scratch.alloc<unsigned long long>((size_t)need);
-    ph_query qc = *q;
-    ph_aggregation cnt{};
-    cnt.type = PH_AGG_COUNT;
-    qc.filter_root = root;
-    qc.num_group_by = 0;
-    qc.group_by = nullptr;
-    qc.num_aggregations = 1;
-    qc.aggregations = &cnt;
-    qc.num_order_by = 0;
-    qc.order_by = nullptr;
-    qc.min_segment_group_trim_size = -1;
-    qc.skip_star_tree = 1;
-    const int64_t off[1] = {0};
-    FilterDocset fd{b.words, off, need};
-    DenseArgs d{0, nullptr, 0, 0, nullptr};
-    d.docset = &fd;
-    ph_segment* one[1] = {seg};
-    std::unique_ptr<ph_result> r(query_execute_impl(ctx, &qc, one, 1, &d));  // drains its stream before it returns
-    b.docs = r->stats.num_docs_scanned;
-    b.entries = r->stats.num_entries_scanned_in_filter;
-    dev_ms += r->stats.device_ms;
-    return b;
-  };
-  std::vector<Bitmap> main_bm(nseg);
-  std::vector<std::vector<Bitmap>> sub_bm(nseg, std::vector<Bitmap>((size_t)K));
+  std::vector<WhereBitmap> main_bm(nseg);
+  std::vector<std::vector<WhereBitmap>> sub_bm(nseg, std::vector<WhereBitmap>((size_t)K));
   for (int i = 0; i < nseg; ++i) {
     if (main_cls[i] == FP_EMPTY) continue;
-    if (main_cls[i] != FP_ALL) main_bm[i] = run_filter(q->filter_root, segs[i]);
+    if (main_cls[i] != FP_ALL) main_bm[i] = where_bitmap(ctx, q, q->filter_root, segs[i], scratch, dev_ms);
     for (int f = 0; f < K; ++f)
-      if (sub_cls[i][f] >= FP_SCAN_LEAF) sub_bm[i][f] = run_filter(sub_roots[f], segs[i]);
+      if (sub_cls[i][f] >= FP_SCAN_LEAF) sub_bm[i][f] = where_bitmap(ctx, q, sub_roots[f], segs[i], scratch, dev_ms);
   }
-  check_interrupt();
+  check_interrupt(q);
+  check_deadline(q);
 
   // ---- stage 2: device segments, chunks, tables
   std::vector<int> fseg_src;
@@ -419,27 +329,7 @@ ph_result* filtered_execute(Context* ctx, const ph_query* q, ph_segment* const* 
       if (c == FP_EMPTY) d.empty |= 1u << p;
       else if (c != FP_ALL) d.mb[p] = sub_bm[i][p - 1].words;
     }
-    for (size_t g = 0; g < group_cols.size(); ++g) {
-      const Column& c = *segs[i]->columns.at(group_cols[g]);
-      if (c.sketch_words || !c.d_fwd.ptr) fail(PH_ERR_UNSUPPORTED, "group-by column " + group_cols[g] + " has no forward index");
-      d.gfwd[g] = c.d_fwd.as<uint32_t>();
-      d.gbits[g] = c.bits;
-      const Dictionary& gd = gdicts[g]->dict;
-      std::vector<int32_t> map((size_t)c.cardinality);
-      bool identity = c.cardinality == gd.size;
-      int64_t j = 0;
-      for (int32_t v = 0; v < c.cardinality; ++v) {
-        while (j < gd.size && gd.compare(j, c.dict, v) < 0) ++j;
-        map[(size_t)v] = (int32_t)j;
-        identity = identity && j == v;
-      }
-      if (!identity) {
-        int32_t* dm = scratch.alloc<int32_t>(map.size());
-        remap_keep.push_back(std::move(map));
-        PH_HIP_CHECK(hipMemcpyAsync(dm, remap_keep.back().data(), 4 * remap_keep.back().size(), hipMemcpyHostToDevice, st));
-        d.gremap[g] = dm;
-      }
-    }
+    group_streams(ks, segs[i], d.gfwd, d.gbits, d.gremap, scratch, remap_keep, st);
     for (int v = 0; v < nvals; ++v) {
       const Column& c = *segs[i]->columns.at(val_cols[(size_t)v]);
       if (!c.d_fwd.ptr || !c.d_values.ptr) fail(PH_ERR_UNSUPPORTED, "value column " + val_cols[(size_t)v] + " has no dictionary table");
@@ -447,9 +337,7 @@ ph_result* filtered_execute(Context* ctx, const ph_query* q, ph_segment* const* 
       d.vtable[v] = c.d_values.ptr;
       d.vbits[v] = c.bits;
     }
-    const int32_t nw = (int32_t)(((int64_t)d.num_docs + 63) / 64);
-    for (int32_t w = 0; w < nw; w += kChunkWords)
-      chunks.push_back(Chunk{(int32_t)fsegs.size(), w, std::min<int32_t>(nw, w + kChunkWords), 0});
+    append_chunks(chunks, (int32_t)fsegs.size(), d.num_docs);
     fseg_src.push_back(i);
     fsegs.push_back(d);
   }
@@ -474,11 +362,7 @@ ph_result* filtered_execute(Context* ctx, const ph_query* q, ph_segment* const* 
     fp.num_slots = ns;
     fp.num_vals = nvals;
     fp.num_group_cols = (int32_t)group_cols.size();
-    int64_t stride = 1;
-    for (int g = (int)group_cols.size() - 1; g >= 0; --g) {
-      fp.group_stride[g] = stride;
-      stride *= std::max<int64_t>(1, gdicts[(size_t)g]->dict.size);
-    }
+    std::copy(ks.stride, ks.stride + kMaxGroupCols, fp.group_stride);
     fp.num_groups = G;
     fp.seg_count = reinterpret_cast<unsigned long long*>(tables);
     fp.pcount = pc_cells ? reinterpret_cast<unsigned long long*>(tables + cnt_cells) : nullptr;
@@ -489,9 +373,7 @@ ph_result* filtered_execute(Context* ctx, const ph_query* q, ph_segment* const* 
                           : ((op == FOP_MAX_I || op == FOP_MAX_F) ? INT64_MIN : 0);
       launch_fill_i64(reinterpret_cast<int64_t*>(fp.slot_out[s]), idv, G, st);
     }
-    const int per_cu = mode == MODE_GROUP_LDS ? 2 : 8;
-    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)chunks.size(), (int64_t)ctx->num_cus * per_cu));
-    launch_scan_filtered(fp, mode, grid, st);
+    launch_scan_filtered(fp, mode, scan_grid(ctx, mode, chunks.size()), st);
     PH_HIP_CHECK(hipEventRecord(lane.lane->ev_stop, st));
     PH_HIP_CHECK(hipMemcpyAsync(host_tables.data(), tables, 8 * cells, hipMemcpyDeviceToHost, st));
     PH_HIP_CHECK(hipStreamSynchronize(st));
@@ -614,17 +496,7 @@ ph_result* filtered_execute(Context* ctx, const ph_query* q, ph_segment* const* 
       if (any) rows.push_back(g);
     }
     const size_t R = rows.size();
-    res->keys.resize(group_cols.size());
-    for (size_t c = 0; c < group_cols.size(); ++c) {
-      const Dictionary& d = gdicts[c]->dict;
-      const int32_t es = entry_size_of(d);
-      res->key_types.push_back(d.type);
-      res->key_entry_size.push_back(es);
-      res->keys[c].assign(R * (size_t)es, 0);
-      const int64_t sz = std::max<int64_t>(1, d.size);
-      for (size_t r = 0; r < R; ++r)
-        put_key(d, (rows[r] / fp.group_stride[c]) % sz, res->keys[c].data() + r * (size_t)es, es);
-    }
+    emit_keys(res.get(), ks, rows);
     for (int k = 0; k < nagg; ++k) {
       res->aggs[(size_t)k].assign(8 * R, 0);
       for (size_t r = 0; r < R; ++r) {
@@ -639,12 +511,7 @@ ph_result* filtered_execute(Context* ctx, const ph_query* q, ph_segment* const* 
     }
     res->num_groups = (int64_t)R;
   }
-  const int plan_mode = mode == MODE_AGG ? 1 : (mode == MODE_GROUP_LDS ? 2 : 3);
-  res->mode = plan_mode;
-  stats.plan_mode = plan_mode;
-  stats.num_devices = 1;
-  stats.device_ms = dev_ms;
-  stats.host_ms = std::max(0.0, std::chrono::duration<double, std::milli>(clock::now() - t0).count() - dev_ms);
+  finish_result(res.get(), mode, dev_ms, t0);
   return res.release();
 }
 

@@ -186,6 +186,10 @@ REFUSALS = [("SELECT COVAR_POP(s, x) FROM t", "STRING column"),
             ("SELECT SUM(x), COVAR_POP(x, y) FROM t", "SUM beside a covariance function"),
             ("SELECT VAR_POP(x), COVAR_POP(x, y) FROM t", "variance function beside a covariance function"),
             ("SELECT COVAR_POP(x, y) FILTER(WHERE f < 3) FROM t", "FILTER clause"),
+            ("SET numGroupsLimit=5; SELECT g, COVAR_POP(x, y) FROM t GROUP BY g",
+             "covariance functions where a segment could reach numGroupsLimit"),
+            ("SET minSegmentGroupTrimSize=1; SELECT g, COVAR_POP(x, y) FROM t GROUP BY g ORDER BY g LIMIT 5",
+             "covariance functions with segment group trim"),
             ("dense", "dense partials")]
 
 

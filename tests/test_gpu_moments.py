@@ -172,6 +172,10 @@ def test_mask_word_edges(ctx, form, n):
 REFUSALS = [("SELECT VAR_POP(s) FROM t", "STRING column"),
             ("SELECT SUM(x), VAR_POP(x) FROM t", "SUM beside a variance function"),
             ("SELECT VAR_POP(x) FILTER(WHERE f < 3) FROM t", "FILTER clause"),
+            ("SET numGroupsLimit=5; SELECT g, VAR_POP(x) FROM t GROUP BY g",
+             "variance functions where a segment could reach numGroupsLimit"),
+            ("SET minSegmentGroupTrimSize=1; SELECT g, VAR_POP(x) FROM t GROUP BY g ORDER BY g LIMIT 5",
+             "variance functions with segment group trim"),
             ("dense", "dense partials")]
 
 

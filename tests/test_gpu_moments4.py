@@ -224,6 +224,10 @@ REFUSALS = [("SELECT SKEWNESS(s) FROM t", "STRING column"),
             ("SELECT SUM(x), SKEWNESS(x) FROM t", "SUM beside a fourth-moment function"),
             ("SELECT VAR_POP(x), KURTOSIS(x) FROM t", "variance function beside a fourth-moment function"),
             ("SELECT SKEWNESS(x) FILTER(WHERE f < 3) FROM t", "FILTER clause"),
+            ("SET numGroupsLimit=5; SELECT g, SKEWNESS(x) FROM t GROUP BY g",
+             "fourth-moment functions where a segment could reach numGroupsLimit"),
+            ("SET minSegmentGroupTrimSize=1; SELECT g, SKEWNESS(x) FROM t GROUP BY g ORDER BY g LIMIT 5",
+             "fourth-moment functions with segment group trim"),
             ("dense", "dense partials")]
 
 
