@@ -275,7 +275,45 @@ typedef struct {
  *     limit);
  *   - key spaces beyond 2^40 keys or the dense table budget (8 bytes, plus 8 per cell and a 40-byte tuple per distinct
  *     column, per key over 32 GB);
- *   - more than 4 distinct argument columns. */
+ *   - more than 4 distinct argument columns.
+ *
+ * PH_AGG_HISTOGRAM: the reference's HistogramAggregationFunction over a pinned single-value INT, LONG, FLOAT or DOUBLE
+ * column (a raw column too).  Its bin edges are entry k of ph_query.histograms (ph_histogram_args), in one of two forms:
+ *   - array form, `HISTOGRAM(col, ARRAY[e0, ..., eB])`: equal_bins == 0, num_edges >= 2 (parseVector,
+ *     HistogramAggregationFunction.java:94-110: "must be greater than 1"), the edges strictly increasing (:105-107),
+ *     B = num_edges - 1; -Infinity / +Infinity may stand as the first / last edge (:99-104);
+ *   - equal-length form, `HISTOGRAM(col, lower, upper, numBins)`: equal_bins = B > 0 (:75), num_edges == 2 with
+ *     {lower, upper} and upper > lower (:73-74).
+ * Anything else (no ph_query.histograms, a null edge list, NaN edges) is PH_ERR_BAD_QUERY, as the reference's
+ * Preconditions (:52-110).  The bin of a value is getBinId (:117-141) evaluated in doubles on the value converted to
+ * double first ((double) of the int64 for LONG: values past 2^53 round; FLOAT widened): val > upper or val < lower is
+ * outside every bin; val == upper is the last bin; else (int) floor((val - lower) / ((upper - lower) / B)) in the
+ * equal-length form and the reference's binary search over the edges in the array form.  Where Java would index out of
+ * bounds -- an equal-length id that reaches B for a value below upper, a NaN value in the array form -- the call is
+ * PH_ERR_UNSUPPORTED, so the CPU plan reproduces the exception; a NaN in the equal-length form goes to bin 0, as
+ * (int) NaN does.  ph_histogram_bin_ids is that evaluation, host-only.
+ * The intermediate result of a row is double[B], the bin counts as the reference's DoubleArrayList holds them, 8 B
+ * bytes per row through ph_result_aggregation / ph_result_aggregation_data.  An aggregation-only query that matched
+ * nothing returns B zeros (extractAggregationResult, :159-166).  A group is a result row when any doc of it matched,
+ * also when every such doc fell outside all bins (setGroupByResult, :288-298, creates the zero vector before it looks at
+ * the bin).  The result column is `histogram(col)` (BaseSingleInputAggregationFunction.getResultColumnName :43-45: the
+ * edges are not part of the name); the DataTable writes the row as OBJECT type 3 (DoubleArrayList), the final result
+ * type is DOUBLE_ARRAY (:184-187).
+ * Served: queries whose aggregations are all HISTOGRAM or COUNT(*), with or without a WHERE clause and a GROUP BY, over
+ * at most 4 distinct (column, bins) pairs of at most 1024 bins each.  ph_exec_stats.scan_kernel is PH_KERNEL_SCAN_BINS;
+ * plan_mode 1 / 2 / 3.  num_docs_scanned is the matched docs, num_entries_scanned_in_filter the WHERE clause's ordinary
+ * statistic, num_entries_scanned_post_filter the matched docs x (group-by columns + distinct argument columns).  Never
+ * answered from a star-tree or from metadata.  Shapes that return PH_ERR_UNSUPPORTED, each with its own message (the CPU
+ * plan serves them):
+ *   - a STRING column, a sketch column or a non-NONE expr_op (an expression argument);
+ *   - any other aggregation beside a HISTOGRAM;
+ *   - a FILTER clause on or beside one;
+ *   - multi-device contexts and the dense-partial entry points;
+ *   - segment group trim (min_segment_group_trim_size > 0 with ORDER BY);
+ *   - a call in which a segment could reach num_groups_limit;
+ *   - key spaces beyond 2^40 keys or the dense table budget (8 bytes, plus 4 per cell and 8 per bin, per key over 32 GB);
+ *   - more than 1024 bins, or more than 4 distinct (column, bins) pairs;
+ *   - a call whose segments hold 2^32 docs or more (the cells are 32-bit until the finish). */
 typedef enum {
   PH_AGG_COUNT = 0,
   PH_AGG_SUM = 1,
@@ -291,7 +329,8 @@ typedef enum {
   PH_AGG_COVARPOP = 11,
   PH_AGG_COVARSAMP = 12,
   PH_AGG_SKEWNESS = 13,
-  PH_AGG_KURTOSIS = 14
+  PH_AGG_KURTOSIS = 14,
+  PH_AGG_HISTOGRAM = 15
 } ph_aggregation_type;
 
 /* 2-operand expression argument of SUM / MIN / MAX: `column <op> column2`, evaluated per row like the reference's
@@ -313,6 +352,15 @@ typedef struct {
   int32_t filter;               /* 0: unfiltered; else 1 + the index in ph_query.filter_nodes of the root of this
                                    aggregation's FILTER(WHERE ...) tree (see "Filtered aggregations" below) */
 } ph_aggregation;
+
+/* The bin edges of a PH_AGG_HISTOGRAM aggregation (see PH_AGG_HISTOGRAM above).  They live beside the aggregation, in
+ * ph_query.histograms, and not in ph_aggregation: an array of ph_aggregation keeps its 56-byte stride for every caller
+ * built against the earlier header.  Entries of other aggregation types are ignored (zero them). */
+typedef struct {
+  const double* hist_edges;     /* array form: the B + 1 edges; equal-length form: {lower, upper} */
+  int32_t hist_num_edges;
+  int32_t hist_equal_bins;      /* 0: array form; B > 0: equal-length form */
+} ph_histogram_args;
 
 /* Filtered aggregations: `agg(...) FILTER(WHERE <filter>)` for COUNT / SUM / MIN / MAX over a plain column (and
  * COUNT(*)), with or without a WHERE clause and a GROUP BY, the reference's FilteredAggregationOperator /
@@ -370,6 +418,8 @@ typedef struct {
   int32_t min_segment_group_trim_size;
   /* query option skipStarTree (QueryContext.isSkipStarTree): 1 = never answer from a segment's star-tree */
   int32_t skip_star_tree;
+  /* NULL, or one entry per aggregation (num_aggregations of them): the bin edges of the PH_AGG_HISTOGRAM ones */
+  const ph_histogram_args* histograms;
 } ph_query;
 
 /* one ORDER BY expression: a group-by column (index into group_by) or an aggregation (index into aggregations) */
@@ -443,8 +493,10 @@ enum {
                                        moments (plan_mode 1, 2 or 3 as the tables live in registers, LDS or HBM) */
   PH_KERNEL_SCAN_COMOMENTS = 22,    /* k_scan_comoments<MODE, FORM, C> + k_comoments_finish: COVAR_POP / COVAR_SAMP as
                                        exact shifted co-moments over a register-direct decode (plan_mode 1, 2 or 3) */
-  PH_KERNEL_SCAN_MOMENTS4 = 23      /* k_scan_moments4<MODE, LAYOUT> + k_moments4_finish: SKEWNESS / KURTOSIS as exact
+  PH_KERNEL_SCAN_MOMENTS4 = 23,     /* k_scan_moments4<MODE, LAYOUT> + k_moments4_finish: SKEWNESS / KURTOSIS as exact
                                        shifted power sums in 32-bit limb cells (plan_mode 1, 2 or 3) */
+  PH_KERNEL_SCAN_BINS = 24          /* k_scan_bins<MODE, REG> + k_bins_finish: HISTOGRAM bin counts, the docs of a wave
+                                       with equal cells combined before the add (plan_mode 1, 2 or 3) */
 };
 
 /* ------------------------------------------------------------------ context */
@@ -478,6 +530,8 @@ int ph_ctx_destroy(ph_ctx* ctx);
  *   count_generic, lds_lean, part_lds, part_flush_first, part_serial: presence -- force the named alternative form
  *   lds_table_max, tile_words, group_reg_lg, interrupt_chunks, part_klo, part_batch_rows, part_depth, part_sets,
  *   part_wg_per_cu, part_slices, part_mm_blind, part_ring_log2: the value
+ *   bins_table_lds_max the bytes of HISTOGRAM bin tables (2 per dictionary entry and slot) a workgroup stages in LDS;
+ *                      larger tables are gathered from HBM (default 32768)
  *   multi_host_merge   presence: a multi-device context merges by group value instead of dense partials
  *   sparse_c           2/4/8: the sparse kernels' register-direct leaf loads (2: every leaf's loads of a step in
  *                      flight at once, leaves <= 8 bits only; 4 -- the default -- / 8: leaf by leaf, fewer registers) */
@@ -543,6 +597,11 @@ int ph_segment_add_star_tree(ph_segment* seg, const ph_star_tree_desc* desc);
 int32_t ph_segment_num_star_trees(const ph_segment* seg);
 /* Host-only parse of a STAR_TREE buffer (OffHeapStarTree's checks: magic, version, header size, node count). */
 int ph_star_tree_check(const void* tree, uint64_t tree_size, int32_t* num_nodes, int32_t* num_dimensions);
+/* Host-only: the HISTOGRAM bin of `count` values of a stored type (`values` in host order: int32, int64, float or
+ * double by data_type), as PH_AGG_HISTOGRAM describes it; out[i] receives the bin, -1 for a value outside every bin.
+ * PH_ERR_BAD_QUERY for malformed edges, PH_ERR_UNSUPPORTED for a value the reference would index out of bounds with. */
+int ph_histogram_bin_ids(const double* edges, int32_t num_edges, int32_t equal_bins, int32_t data_type,
+                         const void* values, int64_t count, int32_t* out);
 /* Host-only parse of a distinctCountHLL__<col> pair's forward index, exactly the validation ph_segment_add_star_tree
  * runs: a var-byte chunk forward index (VarByteChunkForwardIndexWriter versions 2 and 3, any codec of the raw forward
  * indexes) of num_docs serialized HyperLogLogs (int32 BE log2m, int32 BE register bytes, RegisterSet words), every

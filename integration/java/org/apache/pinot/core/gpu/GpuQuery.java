@@ -140,6 +140,32 @@ public final class GpuQuery {
       d.add(ctx.getLimit());
       d.add(ctx.getMinSegmentGroupTrimSize());
       d.add(ctx.isSkipStarTree() ? 1 : 0);
+      // [numHistograms, (aggregation index, equalBins, numEdges, edge bits high, low...)...]: the bin edges of the
+      // HISTOGRAM aggregations (ph_query.histograms), read from the function's own arguments as its constructor reads
+      // them (HistogramAggregationFunction.java:52-84); a FILTER clause on one is not served
+      List<int[]> histograms = new ArrayList<>();
+      for (int i = 0; i < functions.length; i++) {
+        if (functions[i].getType() != AggregationFunctionType.HISTOGRAM) {
+          continue;
+        }
+        FunctionContext call = null;
+        for (java.util.Map.Entry<FunctionContext, Integer> e : ctx.getAggregationFunctionIndexMap().entrySet()) {
+          if (e.getValue() == i) {
+            call = e.getKey();
+          }
+        }
+        int[] h = ctx.hasFilteredAggregations() || call == null ? null : b.histogram(i, call.getArguments());
+        if (h == null) {
+          return null;
+        }
+        histograms.add(h);
+      }
+      d.add(histograms.size());
+      for (int[] h : histograms) {
+        for (int x : h) {
+          d.add(x);
+        }
+      }
       int[] desc = d.stream().mapToInt(Integer::intValue).toArray();
       return new GpuQuery(desc, b._strings.toArray(new String[0]), ctx.getNumGroupsLimit(), ctx.getEndTimeMs());
     } catch (UnsupportedOperationException e) {
@@ -279,6 +305,38 @@ public final class GpuQuery {
       return _preds.size() - 1;
     }
 
+    // HISTOGRAM aggregation `index` with the call's arguments -> {index, equalBins, numEdges, edge bits high, low...}:
+    // (col, lower, upper, numBins) gives equalBins = numBins and the two edges, (col, ARRAY[...]) equalBins = 0 and
+    // the array; null for any other argument list (the CPU plan then reports the reference's own error)
+    int[] histogram(int index, List<ExpressionContext> args) {
+      double[] edges;
+      int equalBins = 0;
+      if (args.size() == 4) {
+        edges = new double[]{args.get(1).getLiteral().getDoubleValue(), args.get(2).getLiteral().getDoubleValue()};
+        equalBins = args.get(3).getLiteral().getIntValue();
+      } else if (args.size() == 2 && args.get(1).getType() == ExpressionContext.Type.FUNCTION
+          && "arrayvalueconstructor".equals(args.get(1).getFunction().getFunctionName())) {
+        List<ExpressionContext> array = args.get(1).getFunction().getArguments();
+        edges = new double[array.size()];
+        for (int i = 0; i < edges.length; i++) {  // "Infinity" arrives as an identifier (:99-104)
+          edges[i] = array.get(i).getType() == ExpressionContext.Type.IDENTIFIER
+              ? Double.parseDouble(array.get(i).getIdentifier()) : array.get(i).getLiteral().getDoubleValue();
+        }
+      } else {
+        return null;
+      }
+      int[] h = new int[3 + 2 * edges.length];
+      h[0] = index;
+      h[1] = equalBins;
+      h[2] = edges.length;
+      for (int i = 0; i < edges.length; i++) {
+        long bits = Double.doubleToRawLongBits(edges[i]);
+        h[3 + 2 * i] = (int) (bits >>> 32);
+        h[4 + 2 * i] = (int) bits;
+      }
+      return h;
+    }
+
     // AggregationFunction -> {type, column, log2m, column2, exprOp, percentile bits high, low, percentileNameForm} or null
     // (not on the GPU path).  The last three are zero unless the function is a PERCENTILE.
     int[] aggregation(AggregationFunction f) {
@@ -312,6 +370,12 @@ public final class GpuQuery {
           break;
         case KURTOSIS:
           type = PinotHipJni.AGG_KURTOSIS;
+          break;
+        case HISTOGRAM:  // bin counts; the edges travel in the descriptor's trailing block (histogram below)
+          if (in.get(0).getType() != ExpressionContext.Type.IDENTIFIER) {
+            return null;
+          }
+          type = PinotHipJni.AGG_HISTOGRAM;
           break;
         default:
           return null;

@@ -66,6 +66,11 @@ final class GpuResultSchema {
       case SKEWNESS:
       case KURTOSIS:
         return new FourthMomentColumn(res, k);
+      case HISTOGRAM:
+        // B, the length of the function's empty result (extractAggregationResult of a fresh holder,
+        // HistogramAggregationFunction.java:159-166)
+        return new BinsColumn(res, k,
+            ((DoubleArrayList) f.extractAggregationResult(f.createAggregationResultHolder())).size());
       default:
         return null;
     }
@@ -127,6 +132,27 @@ final class GpuResultSchema {
       }
       be.flip();
       return org.apache.pinot.segment.local.customobject.PinotFourthMoment.fromBytes(be);
+    }
+  }
+
+  /** HISTOGRAM aggregation {@code k} of a result: double[B] rows in host order, the bin counts -- the DoubleArrayList the
+   *  function's intermediate column (OBJECT, HistogramAggregationFunction.java:179-182) holds. */
+  static final class BinsColumn implements RowObjects {
+    private final ByteBuffer _rows;
+    private final int _bins;
+
+    BinsColumn(long res, int k, int bins) {
+      _bins = bins;
+      _rows = PinotHipJni.resultAggregationBuffer(res, k, 8 * bins).order(ByteOrder.nativeOrder());
+    }
+
+    @Override
+    public Object row(int row) {
+      DoubleArrayList list = new DoubleArrayList(_bins);
+      for (int i = 0; i < _bins; i++) {
+        list.add(_rows.getDouble(8 * (row * _bins + i)));
+      }
+      return list;
     }
   }
 

@@ -143,7 +143,8 @@ JNIEXPORT void JNICALL FN(tableSetColumnType)(JNIEnv* env, jclass c, jlong ctx, 
  *    per group-by column: column,
  *    per aggregation: type, column, log2m, column2, exprOp, percentile bits high, percentile bits low,
  *                     percentileNameForm (the last three zero unless type is PH_AGG_PERCENTILE),
- *    optional: numOrderBy, (kind, index, asc) x numOrderBy, limit, minSegmentGroupTrimSize]
+ *    optional: numOrderBy, (kind, index, asc) x numOrderBy, limit, minSegmentGroupTrimSize, skipStarTree,
+ *    optional: numHistograms, per HISTOGRAM: aggregation index, equalBins, numEdges, (edge bits high, low) x numEdges]
  * decoded into `q`; the arrays it points into are owned by `b` (query_bufs_free).  Returns 0, or -1 for a malformed
  * descriptor (every read is bounds-checked). */
 typedef struct {
@@ -154,10 +155,13 @@ typedef struct {
   ph_order_by* order;
   int32_t* ints;
   const char** vals;
+  ph_histogram_args* hist; /* ph_query.histograms: one per aggregation, the HISTOGRAM ones filled */
+  double* edges;           /* their edges, back to back */
 } query_bufs;
 
 static void query_bufs_free(query_bufs* b) {
   free(b->nodes); free(b->preds); free(b->gby); free(b->aggs); free(b->ints); free(b->vals); free(b->order);
+  free(b->hist); free(b->edges);
 }
 
 static int decode_query(const jint* desc, jsize nd, const char** strs, jsize ns, ph_query* q, query_bufs* b) {
@@ -249,6 +253,32 @@ static int decode_query(const jint* desc, jsize nd, const char** strs, jsize ns,
     NEXT(q->min_segment_group_trim_size);
     q->order_by = b->order;
     if (k < nd) NEXT(q->skip_star_tree); /* QueryContext.isSkipStarTree() */
+    if (k < nd) { /* the bin edges of the HISTOGRAM aggregations (ph_query.histograms) */
+      int nh = 0, ke = 0;
+      NEXT(nh);
+      if (nh < 0 || nh > q->num_aggregations) return -1;
+      b->hist = (ph_histogram_args*)calloc((size_t)q->num_aggregations + 1, sizeof(ph_histogram_args));
+      b->edges = (double*)calloc((size_t)nd + 1, sizeof(double)); /* (an edge takes two descriptor ints) */
+      if (!b->hist || !b->edges) return -1;
+      for (int i = 0; i < nh; ++i) {
+        int at = 0, ne = 0;
+        NEXT(at);
+        if (at < 0 || at >= q->num_aggregations) return -1;
+        NEXT(b->hist[at].hist_equal_bins);
+        NEXT(ne);
+        if (ne < 0 || ne > (nd - k) / 2) return -1;
+        b->hist[at].hist_num_edges = ne;
+        b->hist[at].hist_edges = b->edges + ke;
+        for (int j = 0; j < ne; ++j) {
+          jint hi = 0, lo = 0;
+          NEXT(hi);
+          NEXT(lo);
+          const uint64_t bits = ((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo;
+          memcpy(&b->edges[ke++], &bits, sizeof bits);
+        }
+      }
+      q->histograms = b->hist;
+    }
   }
   /* indices inside the query (children, predicates, root) are range-checked by the library itself */
   q->filter_nodes = b->nodes;

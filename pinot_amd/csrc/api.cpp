@@ -40,7 +40,8 @@ const char* const kOptNames[OPT_COUNT] = {
     "part_serial",
     "part_ring_log2",
     "multi_host_merge",
-    "sparse_c"
+    "sparse_c",
+    "bins_table_lds_max"
 };
 
 void fail(int code, const std::string& msg) { throw Error{code, msg}; }
@@ -236,6 +237,11 @@ int ph_star_tree_check(const void* tree, uint64_t tree_size, int32_t* num_nodes,
   return guarded([&] { ph::star_tree_check_impl(tree, tree_size, num_nodes, num_dimensions); });
 }
 
+int ph_histogram_bin_ids(const double* edges, int32_t num_edges, int32_t equal_bins, int32_t data_type,
+                         const void* values, int64_t count, int32_t* out) {
+  return guarded([&] { ph::histogram_bin_ids(edges, num_edges, equal_bins, data_type, values, count, out); });
+}
+
 int ph_star_tree_hll_pair_check(const void* buf, uint64_t size, int32_t num_docs, int32_t* log2m) {
   return guarded([&] { ph::star_tree_hll_pair_check_impl(buf, size, num_docs, log2m); });
 }
@@ -346,6 +352,12 @@ int ph_query_execute(ph_ctx* ctx, const ph_query* query, ph_segment* const* segm
       if (query->min_segment_group_trim_size > 0 && query->num_group_by > 0 && query->num_order_by > 0)
         fail(PH_ERR_UNSUPPORTED, std::string(fn) + " with segment group trim (minSegmentGroupTrimSize)");
     }
+    if (has_histogram_aggregation(query)) {  // their own plan (bins.cpp): bin counts over a host-made dictId -> bin table
+      bins_validate(query);
+      if (ctx->devs.size() > 1) fail(PH_ERR_UNSUPPORTED, "histograms on a multi-device context");
+      *out = bins_execute(&ctx->c, query, segments, num_segments);
+      return;
+    }
     if (has_moment4_aggregation(query)) {  // their own plan (moments4.cpp): exact shifted power sums in limb cells
       moments4_validate(query);
       if (ctx->devs.size() > 1) fail(PH_ERR_UNSUPPORTED, "fourth-moment functions on a multi-device context");
@@ -454,6 +466,10 @@ static Context* dense_device(ph_ctx* ctx, ph_segment* const* segs, int32_t n) {
 }
 
 static void reject_dense_shapes(const ph_query* q) {
+  if (has_histogram_aggregation(q)) {
+    bins_validate(q);
+    fail(PH_ERR_UNSUPPORTED, "histograms on dense partials");
+  }
   if (has_moment4_aggregation(q)) {
     moments4_validate(q);
     fail(PH_ERR_UNSUPPORTED, "fourth-moment functions on dense partials");

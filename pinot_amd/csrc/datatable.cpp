@@ -131,8 +131,8 @@ std::string agg_column_name(const ph_aggregation& a) {
   // AggregationFunctionType.java:174-181)
   static const char* fn[] = {"count", "sum", "min", "max", "distinctcounthll", "distinctcount", "percentile",
                              "varpop", "varsamp", "stddevpop", "stddevsamp", "covarpop", "covarsamp",
-                             "skewness", "kurtosis"};
-  if (a.type < 0 || a.type > PH_AGG_KURTOSIS) fail(PH_ERR_INVALID_ARGUMENT, "unknown aggregation");
+                             "skewness", "kurtosis", "histogram"};
+  if (a.type < 0 || a.type > PH_AGG_HISTOGRAM) fail(PH_ERR_INVALID_ARGUMENT, "unknown aggregation");
   if (a.type == PH_AGG_COUNT) return "count(*)";
   if (a.type == PH_AGG_COVARPOP || a.type == PH_AGG_COVARSAMP)  // CovarianceAggregationFunction.getResultColumnName
     return std::string(fn[a.type]) + "(" + (a.column ? a.column : "") + "," + (a.column2 ? a.column2 : "") + ")";  // (:72-74)
@@ -267,6 +267,20 @@ std::vector<uint8_t> result_to_datatable(const ph_result* r, const ph_query* q, 
         put_be(dst + 4, 40u, 4);
         var.i32(34);
         for (uint64_t x : f) var.i64((int64_t)x);
+      } else if (t == PH_AGG_HISTOGRAM) {
+        // the row's bin counts, the DoubleArrayList the reference's holder keeps (HistogramAggregationFunction.java:
+        // 159-171), as ObjectType.DoubleArrayList (ObjectSerDeUtils.java:328-357): int size, the doubles
+        const size_t B = r->aggs[k].size() / 8 / (size_t)nrows;
+        const size_t start = var.b.size();
+        var.i32(3);
+        var.i32((int32_t)B);
+        for (size_t b = 0; b < B; ++b) {
+          uint64_t bits;
+          memcpy(&bits, base + ((size_t)g * B + b) * 8, 8);
+          var.i64((int64_t)bits);
+        }
+        put_be(dst, (uint32_t)start, 4);
+        put_be(dst + 4, (uint32_t)(var.b.size() - start - 4), 4);
       } else if (t == PH_AGG_PERCENTILE) {
         // the DoubleArrayList of the matched values (ObjectSerDeUtils.java:328-357): int objectType 3, int size, the
         // doubles -- each value of the row's histogram `count` times, ascending.  The reference writes arrival order

@@ -608,6 +608,57 @@ size_t moments4_lds_bytes(const M4Params& p, int mode, int layout);
 void launch_scan_moments4(const M4Params& p, int mode, int layout, int grid, hipStream_t s);
 void launch_moments4_finish(const M4FinishParams& p, hipStream_t s);
 
+// Histogram bins (scan_bins.hip, bins.cpp): HISTOGRAM(col, lower, upper, numBins) / HISTOGRAM(col, ARRAY[...]).  A slot
+// is one (argument column, bin edges) pair with B bins; a result row holds B + 1 uint32 cells per slot, cell b the
+// matched docs of the row whose value falls in bin b and cell B those whose value is outside every bin, so the cells of
+// any one slot add up to the row's matched docs.  The bin of a doc comes from a per-segment table bin_of[dictId]
+// (uint16, B for "outside") the planner evaluates on the host, in doubles, exactly as the reference's getBinId does.
+constexpr int kBMaxSlots = 4;      // distinct (column, bins) pairs of one query
+constexpr int kBMaxBins = 1024;    // B of one aggregation
+constexpr int kBBallotCells = 8;   // MODE_AGG: a slot of at most this many cells counts by a per-cell ballot loop
+constexpr int kBMatchRounds = 4;   // otherwise: rounds of leader matching before the lanes left add 1 each
+struct BSegment {
+  int32_t num_docs;
+  const unsigned long long* mask;                 // the WHERE clause's doc bitmap; nullptr = every doc
+  const uint32_t* gfwd[kMaxGroupCols];            // group-by column g: packed dictIds, their width, dictId -> key id
+  const int32_t* gremap[kMaxGroupCols];           //   (nullptr: identity)
+  int32_t gbits[kMaxGroupCols];
+  const uint32_t* vfwd[kBMaxSlots];               // slot v: packed dictIds of its column, their width,
+  const uint16_t* bin_of[kBMaxSlots];             //   bin_of[dictId] and the dictionary's entries
+  int32_t vbits[kBMaxSlots];
+  int32_t card[kBMaxSlots];
+};
+struct BParams {
+  const BSegment* segs;
+  const Chunk* chunks;
+  int32_t chunk_begin, chunk_end;
+  int32_t num_slots, num_group_cols;
+  int64_t group_stride[kMaxGroupCols];
+  int64_t num_groups;                             // dense key space (1 without a group-by)
+  int32_t bins[kBMaxSlots];                       // B of slot s
+  int32_t cell_off[kBMaxSlots];                   // first cell of slot s in a row
+  int32_t row_cells;                              // sum of B + 1 over the slots
+  int32_t tab_lds;                                // 1: the segments' bin tables are staged in LDS, slot s at uint16
+  int32_t tab_off[kBMaxSlots];                    //   tab_off[s] of the staging area (tab_bytes in all, 16-aligned)
+  int32_t tab_bytes;
+  uint32_t* cells;                                // zeroed [num_groups][row_cells]
+  unsigned long long* seg_count;                  // zeroed docs per segment
+};
+// k_bins_finish: one wave per (row, slot) sums the slot's B + 1 cells (slot 0's total is the row's matched docs, n) and
+// writes the B counts as doubles, the reference's DoubleArrayList of the row
+struct BFinishParams {
+  int64_t num_groups;
+  int32_t num_slots, row_cells;
+  int32_t bins[kBMaxSlots], cell_off[kBMaxSlots];
+  const uint32_t* cells;
+  unsigned long long* n;                          // [num_groups]
+  double* out[kBMaxSlots];                        // slot s: [num_groups][bins[s]]
+};
+size_t bins_lds_bytes(const BParams& p, int mode);
+// `reg`: MODE_AGG's register-direct decode (every slot's packed width is at most 16 bits)
+void launch_scan_bins(const BParams& p, int mode, bool reg, int grid, hipStream_t s);
+void launch_bins_finish(const BFinishParams& p, hipStream_t s);
+
 // Kernel B of the partitioned group-by: aggregates one batch of records per partition in LDS, then merges
 // the partition's key range into the dense result table (each key range has exactly one owner block).
 struct PartAggParams {
@@ -879,6 +930,7 @@ enum Opt : int {
   OPT_PART_RING_LOG2,
   OPT_MULTI_HOST_MERGE,
   OPT_SPARSE_C,
+  OPT_BINS_TABLE_LDS_MAX,
   OPT_COUNT
 };
 constexpr int64_t kOptUnset = INT64_MIN;
@@ -1269,6 +1321,13 @@ ph_result* comoments_execute(Context* ctx, const ph_query* q, ph_segment* const*
 bool has_moment4_aggregation(const ph_query* q);
 void moments4_validate(const ph_query* q);  // host-only argument and shape checks of such a query
 ph_result* moments4_execute(Context* ctx, const ph_query* q, ph_segment* const* segs, int32_t nseg);
+// histogram bins (bins.cpp): a HISTOGRAM somewhere in the query
+bool has_histogram_aggregation(const ph_query* q);
+void bins_validate(const ph_query* q);  // host-only argument and shape checks of such a query
+ph_result* bins_execute(Context* ctx, const ph_query* q, ph_segment* const* segs, int32_t nseg);
+// getBinId of `count` values of a stored type (host order) into out[i], -1 for a value outside every bin
+void histogram_bin_ids(const double* edges, int32_t num_edges, int32_t equal_bins, int32_t data_type, const void* values,
+                       int64_t count, int32_t* out);
 // FilterContext.toString of the tree rooted at `root` (FilterContext.java:94-114 and each Predicate.toString)
 std::string filter_to_string(const ph_query* q, int32_t root);
 ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const* segs, int32_t nseg,

@@ -124,6 +124,7 @@ WhereBitmap where_bitmap(Context* ctx, const ph_query* q, int32_t root, ph_segme
   qc.order_by = nullptr;
   qc.min_segment_group_trim_size = -1;
   qc.skip_star_tree = 1;
+  qc.histograms = nullptr;
   const int64_t off[1] = {0};
   FilterDocset fd{b.words, off, need};
   DenseArgs d{0, nullptr, 0, 0, nullptr};
@@ -255,7 +256,16 @@ void emit_keys(ph_result* res, const KeySpace& ks, const std::vector<int64_t>& r
 
 void emit_rows(ph_result* res, const ph_query* q, const KeySpace& ks, const unsigned long long* n_host,
                const std::vector<int>& agg_slot, const uint8_t* tuples, size_t tuple_bytes) {
+  int ns = 0;
+  for (int s : agg_slot) ns = std::max(ns, s + 1);
+  emit_rows(res, q, ks, n_host, agg_slot, tuples, std::vector<size_t>((size_t)ns, tuple_bytes));
+}
+
+void emit_rows(ph_result* res, const ph_query* q, const KeySpace& ks, const unsigned long long* n_host,
+               const std::vector<int>& agg_slot, const uint8_t* tuples, const std::vector<size_t>& slot_bytes) {
   const int nagg = q->num_aggregations;
+  std::vector<size_t> slot_base(slot_bytes.size(), 0);  // where slot v's [G] tuples start
+  for (size_t v = 1; v < slot_bytes.size(); ++v) slot_base[v] = slot_base[v - 1] + (size_t)ks.G * slot_bytes[v - 1];
   res->agg_types.resize((size_t)nagg);
   res->agg_log2m.assign((size_t)nagg, 0);
   for (int k = 0; k < nagg; ++k) res->agg_types[(size_t)k] = q->aggregations[k].type;
@@ -269,11 +279,12 @@ void emit_rows(ph_result* res, const ph_query* q, const KeySpace& ks, const unsi
   res->aggs.resize((size_t)nagg);
   for (int k = 0; k < nagg; ++k) {
     const bool count = q->aggregations[k].type == PH_AGG_COUNT;
-    const size_t width = count ? 8 : tuple_bytes;
+    const size_t slot = count ? 0 : (size_t)agg_slot[(size_t)k];
+    const size_t width = count ? 8 : slot_bytes[slot];
     res->aggs[(size_t)k].assign(width * R, 0);
     for (size_t r = 0; r < R; ++r) {
       const void* src = count ? reinterpret_cast<const uint8_t*>(n_host + rows[r])
-                              : tuples + tuple_bytes * ((size_t)ks.G * (size_t)agg_slot[(size_t)k] + (size_t)rows[r]);
+                              : tuples + slot_base[slot] + width * (size_t)rows[r];
       memcpy(res->aggs[(size_t)k].data() + width * r, src, width);
     }
   }

@@ -1,5 +1,5 @@
 // scan_plan.h -- the host-side steps that the bitmap-then-scan plans share: filtered aggregations (filtered.cpp), the
-// variance family (moments.cpp), COVAR (comoments.cpp) and SKEWNESS / KURTOSIS (moments4.cpp).  Each of those planners
+// variance family (moments.cpp), COVAR (comoments.cpp), SKEWNESS / KURTOSIS (moments4.cpp) and HISTOGRAM (bins.cpp).  Each of those planners
 // reads top to bottom as a list of steps; the steps that are the same in all of them live here (scan_plan.cpp), once:
 // the call checks, the range of an argument column, the WHERE clause's class and doc bitmap per segment, the dense key
 // space with its refusals and the mode rule, a segment's group-by streams and chunks, and the assembly of the result.
@@ -101,6 +101,9 @@ void emit_keys(ph_result* res, const KeySpace& ks, const std::vector<int64_t>& r
 // (tuples + tuple_bytes (G slot + key)): the keys with n != 0, or one row for an aggregation-only query
 void emit_rows(ph_result* res, const ph_query* q, const KeySpace& ks, const unsigned long long* n_host,
                const std::vector<int>& agg_slot, const uint8_t* tuples, size_t tuple_bytes);
+// the same with a width per slot (bins.cpp): slot v's tuples, slot_bytes[v] each, [G] of them, follow slot v - 1's
+void emit_rows(ph_result* res, const ph_query* q, const KeySpace& ks, const unsigned long long* n_host,
+               const std::vector<int>& agg_slot, const uint8_t* tuples, const std::vector<size_t>& slot_bytes);
 // plan_mode, num_devices, device_ms, and host_ms = the time since t0 that is not device time
 void finish_result(ph_result* res, int mode, double dev_ms, std::chrono::steady_clock::time_point t0);
 

@@ -19,8 +19,8 @@ from typing import Any, Dict, List, Sequence
 
 import numpy as np
 
-from .query import (COUNT, COVARIANCE_AGGREGATIONS, DISTINCTCOUNT, DISTINCTCOUNTHLL, FOURTHMOMENT_AGGREGATIONS, MAX, MIN,
-                    PERCENTILE, SUM, VARIANCE_AGGREGATIONS, QueryContext)
+from .query import (COUNT, COVARIANCE_AGGREGATIONS, DISTINCTCOUNT, DISTINCTCOUNTHLL, FOURTHMOMENT_AGGREGATIONS,
+                    HISTOGRAM, MAX, MIN, PERCENTILE, SUM, VARIANCE_AGGREGATIONS, QueryContext)
 from .reduce import ResultTable, ValueCounts, merge_intermediate, reduce_groups
 
 # MetadataKey id -> (name, value type) (DataTable.java:103-137); "I" int, "L" long, "S" string
@@ -129,6 +129,14 @@ def double_list_deserialize(b: bytes) -> ValueCounts:
     if 4 + 8 * n != len(b):
         raise ValueError(f"DoubleArrayList of {n} values takes {4 + 8 * n} bytes, the object has {len(b)}")
     return ValueCounts.of(np.frombuffer(b, ">f8", n, 4).astype(np.float64))
+
+
+def histogram_deserialize(b: bytes) -> tuple:
+    """A HISTOGRAM row's bin counts from the same DoubleArrayList bytes: int32 BE size, then the B doubles BE in bin
+    order (HistogramAggregationFunction.java:159-171)."""
+    if len(b) < 4 or 4 + 8 * struct.unpack_from(">i", b, 0)[0] != len(b):
+        raise ValueError(f"DoubleArrayList of {len(b)} bytes")
+    return tuple(np.frombuffer(b, ">f8", (len(b) - 4) // 8, 4).tolist())
 
 
 def variance_deserialize(b: bytes) -> tuple:
@@ -243,6 +251,10 @@ def reduce_datatables(q: QueryContext, tables: Sequence[DataTable]) -> ResultTab
                     otype, payload = v
                     assert otype == DOUBLE_LIST_OBJECT_TYPE
                     v = double_list_deserialize(payload)
+                elif a.function == HISTOGRAM:
+                    otype, payload = v
+                    assert otype == DOUBLE_LIST_OBJECT_TYPE
+                    v = histogram_deserialize(payload)
                 elif a.function in VARIANCE_AGGREGATIONS:
                     otype, payload = v
                     assert otype == VARIANCE_TUPLE_OBJECT_TYPE
@@ -264,6 +276,6 @@ def reduce_datatables(q: QueryContext, tables: Sequence[DataTable]) -> ResultTab
         empty = {f: (0, 0.0, 0.0) for f in VARIANCE_AGGREGATIONS}
         empty.update({f: (0.0, 0.0, 0.0, 0) for f in COVARIANCE_AGGREGATIONS}, COUNT=0)
         empty.update({f: (0,) + (float("nan"),) * 4 for f in FOURTHMOMENT_AGGREGATIONS})
-        groups[()] = [empty.get(a.function) for a in q.aggregations]
+        groups[()] = [(0.0,) * a.num_bins if a.function == HISTOGRAM else empty.get(a.function) for a in q.aggregations]
     keys = list(groups)
     return reduce_groups(q, keys, [groups[k] for k in keys])

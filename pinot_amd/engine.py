@@ -19,7 +19,7 @@ import numpy as np
 
 from . import native as N
 from .query import (COUNT, COVARIANCE_AGGREGATIONS, COVARPOP, COVARSAMP, DISTINCTCOUNT, DISTINCTCOUNTHLL,
-                    FOURTHMOMENT_AGGREGATIONS, KURTOSIS, MAX, MIN, PERCENTILE, SKEWNESS, STDDEVPOP, STDDEVSAMP, SUM,
+                    FOURTHMOMENT_AGGREGATIONS, HISTOGRAM, KURTOSIS, MAX, MIN, PERCENTILE, SKEWNESS, STDDEVPOP, STDDEVSAMP, SUM,
                     VARIANCE_AGGREGATIONS, VARPOP, VARSAMP, FilterContext, QueryContext, parse_sql)
 from .reduce import ResultTable, ValueCounts, reduce_groups
 from .segment import PinnedSegment, SegmentBuffers
@@ -28,7 +28,8 @@ _AGG = {COUNT: N.PH_AGG_COUNT, SUM: N.PH_AGG_SUM, MIN: N.PH_AGG_MIN, MAX: N.PH_A
         DISTINCTCOUNTHLL: N.PH_AGG_DISTINCTCOUNTHLL, DISTINCTCOUNT: N.PH_AGG_DISTINCTCOUNT,
         PERCENTILE: N.PH_AGG_PERCENTILE, VARPOP: N.PH_AGG_VARPOP, VARSAMP: N.PH_AGG_VARSAMP,
         STDDEVPOP: N.PH_AGG_STDDEVPOP, STDDEVSAMP: N.PH_AGG_STDDEVSAMP, COVARPOP: N.PH_AGG_COVARPOP,
-        COVARSAMP: N.PH_AGG_COVARSAMP, SKEWNESS: N.PH_AGG_SKEWNESS, KURTOSIS: N.PH_AGG_KURTOSIS}
+        COVARSAMP: N.PH_AGG_COVARSAMP, SKEWNESS: N.PH_AGG_SKEWNESS, KURTOSIS: N.PH_AGG_KURTOSIS,
+        HISTOGRAM: N.PH_AGG_HISTOGRAM}
 _PRED = {"EQ": N.PH_PRED_EQ, "NOT_EQ": N.PH_PRED_NOT_EQ, "IN": N.PH_PRED_IN, "NOT_IN": N.PH_PRED_NOT_IN,
          "RANGE": N.PH_PRED_RANGE}
 
@@ -64,7 +65,8 @@ SCAN_KERNEL_NAMES = {0: "none", 1: "k_scan", 2: "k_agg_lean", 3: "k_agg_sparse",
                      16: "k_scan, DISTINCTCOUNT bitsets in LDS", 17: "k_scan, DISTINCTCOUNT bitsets in HBM",
                      18: "k_scan, PERCENTILE histograms in LDS", 19: "k_scan, PERCENTILE histograms in HBM",
                      20: "k_scan_filtered", 21: "k_scan_moments + k_moments_finish",
-                     22: "k_scan_comoments + k_comoments_finish", 23: "k_scan_moments4 + k_moments4_finish"}
+                     22: "k_scan_comoments + k_comoments_finish", 23: "k_scan_moments4 + k_moments4_finish",
+                     24: "k_scan_bins + k_bins_finish"}
 
 
 @dataclass
@@ -110,7 +112,8 @@ class IntermediateResult:
     key_columns: List[object]   # per group-by column: numpy array (numeric) or list of str
     # per aggregation: int64 (COUNT), float64 (SUM/MIN/MAX), uint8[n, m] (HLL), DistinctColumn (DISTINCTCOUNT),
     # HistogramColumn (PERCENTILE), VARIANCE_TUPLE_DTYPE records (VARPOP / VARSAMP / STDDEVPOP / STDDEVSAMP),
-    # COVARIANCE_TUPLE_DTYPE records (COVARPOP / COVARSAMP), FOURTHMOMENT_TUPLE_DTYPE records (SKEWNESS / KURTOSIS)
+    # COVARIANCE_TUPLE_DTYPE records (COVARPOP / COVARSAMP), FOURTHMOMENT_TUPLE_DTYPE records (SKEWNESS / KURTOSIS),
+    # float64[n, B] bin counts (HISTOGRAM)
     agg_columns: List[object]
     num_groups: int
     functions: List[str]
@@ -136,6 +139,8 @@ class IntermediateResult:
                 conv.append([col.value_set(i) for i in range(self.num_groups)])
             elif f == PERCENTILE:  # value multisets: partial results of different calls merge by value
                 conv.append([col.value_counts(i) for i in range(self.num_groups)])
+            elif f == HISTOGRAM:  # the row's B bin counts
+                conv.append([tuple(t) for t in col.tolist()])
             elif f in VARIANCE_AGGREGATIONS + COVARIANCE_AGGREGATIONS + FOURTHMOMENT_AGGREGATIONS:
                 # (count, sum, m2) / (sum_x, sum_y, sum_xy, count) / (n, m1, m2, m3, m4)
                 conv.append([tuple(t) for t in col.tolist()])
@@ -219,7 +224,16 @@ class _QueryStruct:
                                     int(a.name_form) if a.function == PERCENTILE else 0, f)
               for a, f in zip(q.aggregations, agg_filter)])
         aggs = ctypes.cast(agg_arr, ctypes.POINTER(N.Aggregation))
-        self.keep += [node_arr, pred_arr, gb, agg_arr]
+        # the bin edges of the HISTOGRAM aggregations, one ph_histogram_args per aggregation (none: a null pointer)
+        hist_arr = None
+        if any(a.function == HISTOGRAM for a in q.aggregations):
+            hist_arr = (N.HistogramArgs * len(q.aggregations))()
+            for k, a in enumerate(q.aggregations):
+                if a.function == HISTOGRAM:
+                    edges = (ctypes.c_double * len(a.edges))(*a.edges)
+                    self.keep.append(edges)
+                    hist_arr[k] = N.HistogramArgs(edges, len(a.edges), a.equal_bins)
+        self.keep += [node_arr, pred_arr, gb, agg_arr, hist_arr]
         end_ms = 0
         if "timeoutMs" in q.options:
             import time
@@ -237,7 +251,7 @@ class _QueryStruct:
                               len(q.aggregations), aggs, q.num_groups_limit, end_ms,
                               ctypes.pointer(interrupt) if interrupt is not None else None,
                               len(obs), ob_arr, int(q.limit), seg_trim,
-                              int(str(q.options.get("skipStarTree", "false")).lower() == "true"))
+                              int(str(q.options.get("skipStarTree", "false")).lower() == "true"), hist_arr)
 
 
 # a variance function's result row: the reference's VarianceTuple (VarianceTuple.java:25-33) in host order
@@ -278,7 +292,7 @@ OPTION_NAMES = ("roaring_atomic", "agg_cont", "group_cont", "disable_partition",
                 "lds_generic", "count_generic", "lds_lean", "group_reg_lg", "stat_fuse", "interrupt_chunks",
                 "part_klo", "part_batch_rows", "part_flush_first", "part_depth", "part_lds", "part_sets",
                 "part_wg_per_cu", "part_slices", "part_mm_blind", "part_serial", "part_ring_log2", "multi_host_merge",
-                "sparse_c")
+                "sparse_c", "bins_table_lds_max")
 OPTION_UNSET = -(1 << 63)
 
 
@@ -472,6 +486,8 @@ class GpuContext:
                 finals = np.zeros(n, np.float64)
                 N.check(L.ph_result_percentile_final(r, k, finals.ctypes.data))
                 arr = HistogramColumn(hist[:, :d], values, finals)
+            elif a.function == HISTOGRAM:
+                arr = view(L.ph_result_aggregation_data(r, k), 8 * a.num_bins * n).view(np.float64).reshape(n, a.num_bins)
             elif a.function in VARIANCE_AGGREGATIONS:
                 arr = view(L.ph_result_aggregation_data(r, k), 24 * n).view(VARIANCE_TUPLE_DTYPE)
             elif a.function in COVARIANCE_AGGREGATIONS:

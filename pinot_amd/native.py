@@ -26,7 +26,7 @@ PH_PRED_EQ, PH_PRED_NOT_EQ, PH_PRED_IN, PH_PRED_NOT_IN, PH_PRED_RANGE = range(5)
 PH_FILTER_AND, PH_FILTER_OR, PH_FILTER_NOT, PH_FILTER_PREDICATE = range(4)
 (PH_AGG_COUNT, PH_AGG_SUM, PH_AGG_MIN, PH_AGG_MAX, PH_AGG_DISTINCTCOUNTHLL, PH_AGG_DISTINCTCOUNT,
  PH_AGG_PERCENTILE, PH_AGG_VARPOP, PH_AGG_VARSAMP, PH_AGG_STDDEVPOP, PH_AGG_STDDEVSAMP, PH_AGG_COVARPOP,
- PH_AGG_COVARSAMP, PH_AGG_SKEWNESS, PH_AGG_KURTOSIS) = range(15)
+ PH_AGG_COVARSAMP, PH_AGG_SKEWNESS, PH_AGG_KURTOSIS, PH_AGG_HISTOGRAM) = range(16)
 
 
 class PinotHipError(RuntimeError):
@@ -102,6 +102,13 @@ PH_KERNEL_SCAN_FILTERED = 20
 PH_KERNEL_SCAN_MOMENTS = 21
 PH_KERNEL_SCAN_COMOMENTS = 22
 PH_KERNEL_SCAN_MOMENTS4 = 23
+PH_KERNEL_SCAN_BINS = 24
+
+
+class HistogramArgs(ctypes.Structure):
+    """ph_histogram_args: entry k of ph_query.histograms holds the bin edges of aggregation k when it is a HISTOGRAM."""
+    _fields_ = [("hist_edges", ctypes.POINTER(ctypes.c_double)), ("hist_num_edges", ctypes.c_int32),
+                ("hist_equal_bins", ctypes.c_int32)]
 
 
 class OrderBy(ctypes.Structure):
@@ -119,7 +126,8 @@ class Query(ctypes.Structure):
                 ("aggregations", ctypes.POINTER(Aggregation)), ("num_groups_limit", ctypes.c_int64),
                 ("end_time_ms", ctypes.c_int64), ("interrupt", ctypes.POINTER(ctypes.c_int32)),
                 ("num_order_by", ctypes.c_int32), ("order_by", ctypes.POINTER(OrderBy)), ("limit", ctypes.c_int32),
-                ("min_segment_group_trim_size", ctypes.c_int32), ("skip_star_tree", ctypes.c_int32)]
+                ("min_segment_group_trim_size", ctypes.c_int32), ("skip_star_tree", ctypes.c_int32),
+                ("histograms", ctypes.POINTER(HistogramArgs))]
 
 
 PH_MAX_DENSE_TABLES = 16
@@ -156,7 +164,7 @@ EXPORTED_SYMBOLS = (
     "ph_query_dense_layout", "ph_query_execute_dense", "ph_dense_finalize", "ph_fixed_bit_pack",
     "ph_raw_forward_index_read", "ph_index_map_lookup", "ph_result_datatable", "ph_selftest_unpack",
     "ph_selftest_unpack_staged", "ph_last_error", "ph_version", "ph_segment_add_star_tree", "ph_segment_num_star_trees",
-    "ph_star_tree_check", "ph_star_tree_hll_pair_check",
+    "ph_star_tree_check", "ph_star_tree_hll_pair_check", "ph_histogram_bin_ids",
     "ph_result_distinct_dictionary", "ph_result_distinct_values", "ph_result_distinct_words",
     "ph_result_distinct_counts",
     "ph_result_percentile_dictionary", "ph_result_percentile_values", "ph_result_percentile_final",
@@ -249,6 +257,7 @@ def lib():
         "ph_segment_num_star_trees": ([vp], i32),
         "ph_star_tree_check": ([vp, ctypes.c_uint64, ctypes.POINTER(i32), ctypes.POINTER(i32)], ctypes.c_int),
         "ph_star_tree_hll_pair_check": ([vp, ctypes.c_uint64, i32, ctypes.POINTER(i32)], ctypes.c_int),
+        "ph_histogram_bin_ids": ([vp, i32, i32, i32, vp, i64, vp], ctypes.c_int),
         "ph_last_error": ([], ctypes.c_char_p),
         "ph_version": ([], ctypes.c_char_p),
     }

@@ -18,6 +18,7 @@ Reference anchors
 """
 from __future__ import annotations
 
+import math
 import re
 from dataclasses import dataclass, field
 from typing import List, Optional, Sequence, Tuple, Union
@@ -40,6 +41,9 @@ COVARIANCE_AGGREGATIONS = (COVARPOP, COVARSAMP)
 # holder; FOURTHMOMENT itself has no final result there (:165-168) and stays an unsupported function
 SKEWNESS, KURTOSIS = "SKEWNESS", "KURTOSIS"
 FOURTHMOMENT_AGGREGATIONS = (SKEWNESS, KURTOSIS)
+# HISTOGRAM(col, lower, upper, numBins) / HISTOGRAM(col, ARRAY[e0, ..., eB]) (HistogramAggregationFunction.java:52-84): a
+# DoubleArrayList of B bin counts per result holder
+HISTOGRAM = "HISTOGRAM"
 SUPPORTED_AGGREGATIONS = ((COUNT, SUM, MIN, MAX, DISTINCTCOUNTHLL, DISTINCTCOUNT, PERCENTILE) + VARIANCE_AGGREGATIONS
                           + COVARIANCE_AGGREGATIONS + FOURTHMOMENT_AGGREGATIONS)
 DEFAULT_HLL_LOG2M = 8  # CommonConstants.Helix.DEFAULT_HYPERLOGLOG_LOG2M (CommonConstants.java:96-97)
@@ -203,6 +207,13 @@ class AggregationSpec:
     # agg(...) FILTER(WHERE <filter>): the function aggregates the docs of WHERE AND <filter>
     # (AggregationFunctionUtils.buildFilteredAggregateProjectOperators, AggregationFunctionUtils.java:191-267)
     filter: Optional[FilterContext] = None
+    # HISTOGRAM: the B + 1 edges of the ARRAY form (equal_bins 0), or (lower, upper) with equal_bins = B
+    edges: Tuple[float, ...] = ()
+    equal_bins: int = 0
+
+    @property
+    def num_bins(self) -> int:
+        return self.equal_bins or len(self.edges) - 1
 
     def columns(self) -> List[str]:
         return [c for c in (self.column, self.column2) if c]
@@ -275,7 +286,7 @@ class QueryContext:
 # --------------------------------------------------------------------------- SQL subset parser
 _TOKEN = re.compile(
     r"\s*(?:(?P<num>-?\d+(?:\.\d+)?(?:[eE][-+]?\d+)?)|(?P<str>'(?:[^']|'')*')|(?P<id>[A-Za-z_][A-Za-z0-9_.$]*)"
-    r"|(?P<op><>|!=|<=|>=|=|<|>|\(|\)|,|\*|;|\+|-))")
+    r"|(?P<qid>\"[^\"]*\")|(?P<op><>|!=|<=|>=|=|<|>|\(|\)|\[|\]|,|\*|;|\+|-))")
 
 _KEYWORDS = {"SELECT", "FROM", "WHERE", "GROUP", "BY", "ORDER", "LIMIT", "AND", "OR", "NOT", "IN",
              "BETWEEN", "AS", "ASC", "DESC", "SET", "TOP"}
@@ -354,8 +365,60 @@ class _Parser:
             self.expect("op", ")")
         return agg
 
+    def histogram_call(self) -> AggregationSpec:
+        """HISTOGRAM(col, ARRAY[e0, ..., eB]) | HISTOGRAM(col, lower, upper, numBins), with the reference's argument checks
+        (HistogramAggregationFunction.java:52-110)."""
+        def number() -> float:
+            t = self.take()
+            if t[0] == "qid":  # "Infinity" / "-Infinity": an identifier the reference parses as a double (:99-102)
+                t = ("num", t[1][1:-1])
+            if t[0] not in ("num", "str"):
+                raise SqlParseError(f"expected a number, got {t}")
+            try:
+                return float(t[1].strip("'"))
+            except ValueError:
+                raise SqlParseError(f"expected a number, got {t}")
+
+        col = self.ident()
+        if self.peek() != ("op", ","):
+            raise SqlParseError("Histogram expects 2 or 4 arguments, got: 1")
+        self.i += 1
+        t = self.peek()
+        if t[0] == "id" and t[1].upper() == "ARRAY":
+            self.i += 1
+            self.expect("op", "[")
+            edges = [number()]
+            while self.accept("op", ","):
+                edges.append(number())
+            self.expect("op", "]")
+            if len(edges) < 2:
+                raise SqlParseError("The number of bin edges must be greater than 1")
+            if any(not b > a for a, b in zip(edges, edges[1:])):
+                raise SqlParseError("The bin edges must be strictly increasing")
+            if self.accept("op", ","):
+                raise SqlParseError("Histogram expects 2 or 4 arguments")
+            self.expect("op", ")")
+            return AggregationSpec(HISTOGRAM, col, edges=tuple(edges))
+        args = [number()]
+        while self.accept("op", ","):
+            args.append(number())
+        self.expect("op", ")")
+        if len(args) == 1:
+            raise SqlParseError("Please use the format of `Histogram(columnName, ARRAY[1,10,100])` to specify the bin edges")
+        if len(args) != 3:
+            raise SqlParseError(f"Histogram expects 2 or 4 arguments, got: {len(args) + 1}")
+        lower, upper, bins = args
+        if not upper > lower:
+            raise SqlParseError(f"The right most edge must be greater than left most edge, given {lower} and {upper}")
+        if not math.isfinite(bins) or bins != int(bins) or bins <= 0:
+            raise SqlParseError(f"The number of bins must be greater than zero, given {bins}")
+        return AggregationSpec(HISTOGRAM, col, edges=(lower, upper), equal_bins=int(bins))
+
     def plain_agg_call(self) -> Optional[AggregationSpec]:
         t, n = self.peek(), self.peek(1)
+        if t[0] == "id" and t[1].upper() == HISTOGRAM and n == ("op", "("):
+            self.i += 2
+            return self.histogram_call()
         pm = re.fullmatch(r"PERCENTILE(\d*)", t[1].upper()) if t[0] == "id" and n == ("op", "(") else None
         if pm:  # PERCENTILE(col, p) | PERCENTILEnn(col)  (AggregationFunctionFactory.java:72-128)
             self.i += 2

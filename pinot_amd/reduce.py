@@ -30,7 +30,7 @@ from typing import Any, List, Sequence
 import numpy as np
 
 from .query import (COUNT, COVARIANCE_AGGREGATIONS, COVARSAMP, DISTINCTCOUNT, DISTINCTCOUNTHLL,
-                    FOURTHMOMENT_AGGREGATIONS, MAX, MIN, PERCENTILE, SKEWNESS, STDDEVPOP, STDDEVSAMP, SUM,
+                    FOURTHMOMENT_AGGREGATIONS, HISTOGRAM, MAX, MIN, PERCENTILE, SKEWNESS, STDDEVPOP, STDDEVSAMP, SUM,
                     VARIANCE_AGGREGATIONS, VARSAMP, QueryContext)
 
 
@@ -277,6 +277,8 @@ def merge_intermediate(function: str, a, b):
         return frozenset(a) | frozenset(b)
     if function == PERCENTILE:
         return a.merge(b)
+    if function == HISTOGRAM:  # DoubleVectorOpUtils.vectorAdd (HistogramAggregationFunction.merge :174-177)
+        return tuple(float(x) + float(y) for x, y in zip(a, b))
     if function in VARIANCE_AGGREGATIONS:
         return variance_merge(a, b)
     if function in COVARIANCE_AGGREGATIONS:
@@ -304,6 +306,8 @@ def final_value(spec, value):
         return len(value)
     if spec.function == PERCENTILE:
         return percentile_final(value, spec.percentile)
+    if spec.function == HISTOGRAM:  # DOUBLE_ARRAY: the list of doubles (extractFinalResult returns the list)
+        return [float(x) for x in value]
     if spec.function in VARIANCE_AGGREGATIONS:
         return variance_final(value, spec.function)
     if spec.function in COVARIANCE_AGGREGATIONS:
