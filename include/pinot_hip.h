@@ -313,7 +313,49 @@ typedef struct {
  *   - a call in which a segment could reach num_groups_limit;
  *   - key spaces beyond 2^40 keys or the dense table budget (8 bytes, plus 4 per cell and 8 per bin, per key over 32 GB);
  *   - more than 1024 bins, or more than 4 distinct (column, bins) pairs;
- *   - a call whose segments hold 2^32 docs or more (the cells are 32-bit until the finish). */
+ *   - a call whose segments hold 2^32 docs or more (the cells are 32-bit until the finish).
+ *
+ * PH_AGG_FIRSTWITHTIME / PH_AGG_LASTWITHTIME: the reference's FIRSTWITHTIME / LASTWITHTIME(dataCol, timeCol, 'type')
+ * (AggregationFunctionFactory.java:201-254) over pinned single-value INT, LONG, FLOAT or DOUBLE columns (raw columns
+ * too): `column` is the data column, `column2` the time column with expr_op PH_EXPR_NONE, and the declared type is entry
+ * k of ph_query.with_time (ph_with_time_args); a with-time aggregation without its entry is PH_ERR_BAD_QUERY.
+ *   - The time of a doc is timeValSet.getLongValuesSV() (LastIntValueWithTimeAggregationFunction.java:71): exact for
+ *     an INT / LONG column, Java's (long) cast for FLOAT / DOUBLE (truncation toward zero, saturation, NaN -> 0).
+ *   - Within a segment docs arrive in ascending docId; LAST replaces on `time >= lastTime`
+ *     (LastWithTimeAggregationFunction.java:123-128, 172-177), FIRST on `time <= firstTime`
+ *     (FirstWithTimeAggregationFunction.java:122-127, 171-176): in both, among the docs with the extreme time the one with
+ *     the largest docId wins.
+ *   - Across segments merge keeps its first argument on equal times (:200-206); the reference's combine order depends
+ *     on its threads, so this plan pins one: on equal time the segment earlier in the call's segment list wins
+ *     (parity unpinned).
+ *   - The intermediate result of a row is the (value, time) pair, 16 bytes {int64 or double value; int64 time} through
+ *     ph_result_aggregation / ph_result_aggregation_data: the value is int64 for declared INT / LONG and double for FLOAT
+ *     / DOUBLE (FLOAT holds (double)(float)).  A row with no doc holds the subclass's DEFAULT_VALUE_TIME_PAIR
+ *     (Last|First{Int,Long,Float,Double}ValueWithTimeAggregationFunction.java:42-44): value Integer.MIN_VALUE,
+ *     Long.MIN_VALUE or NaN, time Long.MIN_VALUE for LAST and Long.MAX_VALUE for FIRST.  The final result is the value,
+ *     its column type the declared type; the result column is getResultColumnName() of the subclass,
+ *     `lastwithtime(x,ts,'LONG')`; the DataTable writes the pair as OBJECT type 27 / 28 / 29 / 30 (IntLongPair,
+ *     LongLongPair, FloatLongPair, DoubleLongPair: the value at its own width, then the 8-byte time, big-endian).
+ * Served: queries whose aggregations are all FIRSTWITHTIME / LASTWITHTIME or COUNT(*), with or without a WHERE clause
+ * and a GROUP BY, over at most 4 distinct (time column, direction) pairs; aggregations over one pair share one scan
+ * cell whatever their data columns.  ph_exec_stats.scan_kernel is PH_KERNEL_SCAN_WITHTIME; plan_mode 1 / 2 / 3.
+ * num_docs_scanned is the matched docs, num_entries_scanned_in_filter the WHERE clause's ordinary statistic,
+ * num_entries_scanned_post_filter the matched docs x (group-by columns + distinct data and time columns).  Never
+ * answered from a star-tree or from metadata.  Shapes that return PH_ERR_UNSUPPORTED, each with its own message (the CPU
+ * plan serves them):
+ *   - declared type STRING (BOOLEAN has no ph_data_type code: a caller refuses it itself);
+ *   - a declared type that is neither the data column's stored type nor an exact widening of it (INT -> LONG,
+ *     INT -> DOUBLE, FLOAT -> DOUBLE);
+ *   - a STRING or sketch data or time column, or a non-NONE expr_op (an expression argument);
+ *   - any other aggregation beside one;
+ *   - a FILTER clause on or beside one;
+ *   - multi-device contexts and the dense-partial entry points;
+ *   - segment group trim (min_segment_group_trim_size > 0 with ORDER BY);
+ *   - a call in which a segment could reach num_groups_limit;
+ *   - key spaces beyond 2^40 keys or the dense table budget (8 bytes, plus 8 per pair and 16 per aggregation, per key
+ *     over 32 GB);
+ *   - more than 4 distinct (time column, direction) pairs;
+ *   - a call whose segments hold 2^32 - 1 docs or more (a doc's position is the low word of its key). */
 typedef enum {
   PH_AGG_COUNT = 0,
   PH_AGG_SUM = 1,
@@ -330,7 +372,9 @@ typedef enum {
   PH_AGG_COVARSAMP = 12,
   PH_AGG_SKEWNESS = 13,
   PH_AGG_KURTOSIS = 14,
-  PH_AGG_HISTOGRAM = 15
+  PH_AGG_HISTOGRAM = 15,
+  PH_AGG_FIRSTWITHTIME = 16,
+  PH_AGG_LASTWITHTIME = 17
 } ph_aggregation_type;
 
 /* 2-operand expression argument of SUM / MIN / MAX: `column <op> column2`, evaluated per row like the reference's
@@ -361,6 +405,13 @@ typedef struct {
   int32_t hist_num_edges;
   int32_t hist_equal_bins;      /* 0: array form; B > 0: equal-length form */
 } ph_histogram_args;
+
+/* The declared type of a PH_AGG_FIRSTWITHTIME / PH_AGG_LASTWITHTIME aggregation (see above), the function's third
+ * argument.  It lives beside the aggregation, in ph_query.with_time, for the reason ph_histogram_args does.  Entries of
+ * other aggregation types are ignored (zero them). */
+typedef struct {
+  int32_t data_type;            /* ph_data_type: PH_INT, PH_LONG, PH_FLOAT or PH_DOUBLE */
+} ph_with_time_args;
 
 /* Filtered aggregations: `agg(...) FILTER(WHERE <filter>)` for COUNT / SUM / MIN / MAX over a plain column (and
  * COUNT(*)), with or without a WHERE clause and a GROUP BY, the reference's FilteredAggregationOperator /
@@ -420,6 +471,8 @@ typedef struct {
   int32_t skip_star_tree;
   /* NULL, or one entry per aggregation (num_aggregations of them): the bin edges of the PH_AGG_HISTOGRAM ones */
   const ph_histogram_args* histograms;
+  /* NULL, or one entry per aggregation: the declared types of the PH_AGG_FIRSTWITHTIME / PH_AGG_LASTWITHTIME ones */
+  const ph_with_time_args* with_time;
 } ph_query;
 
 /* one ORDER BY expression: a group-by column (index into group_by) or an aggregation (index into aggregations) */
@@ -495,8 +548,11 @@ enum {
                                        exact shifted co-moments over a register-direct decode (plan_mode 1, 2 or 3) */
   PH_KERNEL_SCAN_MOMENTS4 = 23,     /* k_scan_moments4<MODE, LAYOUT> + k_moments4_finish: SKEWNESS / KURTOSIS as exact
                                        shifted power sums in 32-bit limb cells (plan_mode 1, 2 or 3) */
-  PH_KERNEL_SCAN_BINS = 24          /* k_scan_bins<MODE, REG> + k_bins_finish: HISTOGRAM bin counts, the docs of a wave
+  PH_KERNEL_SCAN_BINS = 24,         /* k_scan_bins<MODE, REG> + k_bins_finish: HISTOGRAM bin counts, the docs of a wave
                                        with equal cells combined before the add (plan_mode 1, 2 or 3) */
+  PH_KERNEL_SCAN_WITHTIME = 25      /* k_scan_withtime<MODE, REG> + k_withtime_finish: FIRSTWITHTIME / LASTWITHTIME as a
+                                       64-bit maximum of (time rank, doc position) keys, the data columns gathered once
+                                       per result cell (plan_mode 1, 2 or 3) */
 };
 
 /* ------------------------------------------------------------------ context */
@@ -532,6 +588,10 @@ int ph_ctx_destroy(ph_ctx* ctx);
  *   part_wg_per_cu, part_slices, part_mm_blind, part_ring_log2: the value
  *   bins_table_lds_max the bytes of HISTOGRAM bin tables (2 per dictionary entry and slot) a workgroup stages in LDS;
  *                      larger tables are gathered from HBM (default 32768)
+ *   withtime_table_lds_max the same for the FIRSTWITHTIME / LASTWITHTIME time-rank tables (4 bytes per dictionary entry
+ *                      and slot; default 32768)
+ *   withtime_no_combine presence: the with-time group-by scan issues one atomic per doc that passes its screen, without
+ *                      combining the equal rows of a wave first (for measurements)
  *   multi_host_merge   presence: a multi-device context merges by group value instead of dense partials
  *   sparse_c           2/4/8: the sparse kernels' register-direct leaf loads (2: every leaf's loads of a step in
  *                      flight at once, leaves <= 8 bits only; 4 -- the default -- / 8: leaf by leaf, fewer registers) */
@@ -659,7 +719,9 @@ const void* ph_result_key_data(const ph_result* r, int32_t group_by_index);
  * (PERCENTILE aggregations over one column return the same histogram),
  * VARPOP / VARSAMP / STDDEVPOP / STDDEVSAMP {int64 count; double sum; double m2}, 24 bytes (see PH_AGG_VARPOP),
  * COVARPOP / COVARSAMP {double sum_x; double sum_y; double sum_xy; int64 count}, 32 bytes (see PH_AGG_COVARPOP),
- * SKEWNESS / KURTOSIS {int64 n; double m1; double m2; double m3; double m4}, 40 bytes (see PH_AGG_SKEWNESS) */
+ * SKEWNESS / KURTOSIS {int64 n; double m1; double m2; double m3; double m4}, 40 bytes (see PH_AGG_SKEWNESS),
+ * FIRSTWITHTIME / LASTWITHTIME {int64 or double value; int64 time}, 16 bytes: the value is int64 for a declared INT /
+ * LONG and double for FLOAT / DOUBLE (see PH_AGG_FIRSTWITHTIME) */
 int ph_result_aggregation(const ph_result* r, int32_t aggregation_index, void* out);
 const void* ph_result_aggregation_data(const ph_result* r, int32_t aggregation_index);
 /* DISTINCTCOUNT aggregation k.  Its result dictionary is the table dictionary of the column (ph_table_set_dictionary)

@@ -166,6 +166,38 @@ public final class GpuQuery {
           d.add(x);
         }
       }
+      // [numWithTime, (aggregation index, declared data type)...]: the declared types of the FIRSTWITHTIME / LASTWITHTIME
+      // aggregations (ph_query.with_time), read from the subclass's final result type (BOOLEAN and STRING: not served)
+      List<int[]> withTime = new ArrayList<>();
+      for (int i = 0; i < functions.length; i++) {
+        AggregationFunctionType t = functions[i].getType();
+        if (t != AggregationFunctionType.FIRSTWITHTIME && t != AggregationFunctionType.LASTWITHTIME) {
+          continue;
+        }
+        int dataType;
+        switch (functions[i].getFinalResultColumnType()) {
+          case INT:
+            dataType = PinotHipJni.INT;
+            break;
+          case LONG:
+            dataType = PinotHipJni.LONG;
+            break;
+          case FLOAT:
+            dataType = PinotHipJni.FLOAT;
+            break;
+          case DOUBLE:
+            dataType = PinotHipJni.DOUBLE;
+            break;
+          default:
+            return null;
+        }
+        withTime.add(new int[]{i, dataType});
+      }
+      d.add(withTime.size());
+      for (int[] w : withTime) {
+        d.add(w[0]);
+        d.add(w[1]);
+      }
       int[] desc = d.stream().mapToInt(Integer::intValue).toArray();
       return new GpuQuery(desc, b._strings.toArray(new String[0]), ctx.getNumGroupsLimit(), ctx.getEndTimeMs());
     } catch (UnsupportedOperationException e) {
@@ -377,10 +409,25 @@ public final class GpuQuery {
           }
           type = PinotHipJni.AGG_HISTOGRAM;
           break;
+        case FIRSTWITHTIME:  // the (value, time) pair of the doc with the extreme time (GpuResultSchema.PairColumn)
+          type = PinotHipJni.AGG_FIRSTWITHTIME;
+          break;
+        case LASTWITHTIME:
+          type = PinotHipJni.AGG_LASTWITHTIME;
+          break;
         default:
           return null;
       }
       ExpressionContext e = in.get(0);
+      if (type == PinotHipJni.AGG_FIRSTWITHTIME || type == PinotHipJni.AGG_LASTWITHTIME) {
+        // getInputExpressions is (dataCol, timeCol) (LastWithTimeAggregationFunction.java:208-211); the declared type
+        // travels in the descriptor's trailing block; an expression argument is not served
+        if (in.size() != 2 || e.getType() != ExpressionContext.Type.IDENTIFIER
+            || in.get(1).getType() != ExpressionContext.Type.IDENTIFIER) {
+          return null;
+        }
+        return new int[]{type, str(e.getIdentifier()), 0, str(in.get(1).getIdentifier()), PinotHipJni.EXPR_NONE, 0, 0, 0};
+      }
       if (type == PinotHipJni.AGG_PERCENTILE) {
         if (e.getType() != ExpressionContext.Type.IDENTIFIER) {
           return null;

@@ -71,6 +71,9 @@ final class GpuResultSchema {
         // HistogramAggregationFunction.java:159-166)
         return new BinsColumn(res, k,
             ((DoubleArrayList) f.extractAggregationResult(f.createAggregationResultHolder())).size());
+      case FIRSTWITHTIME:
+      case LASTWITHTIME:
+        return new PairColumn(res, k, f.getFinalResultColumnType());
       default:
         return null;
     }
@@ -153,6 +156,34 @@ final class GpuResultSchema {
         list.add(_rows.getDouble(8 * (row * _bins + i)));
       }
       return list;
+    }
+  }
+
+  /** FIRSTWITHTIME / LASTWITHTIME aggregation {@code k} of a result: 16-byte rows in host order, {long or double value;
+   *  long time} -- the ValueLongPair of the declared type the function's intermediate column (OBJECT,
+   *  LastWithTimeAggregationFunction.java:213-216) holds. */
+  static final class PairColumn implements RowObjects {
+    private final ByteBuffer _rows;
+    private final ColumnDataType _type;
+
+    PairColumn(long res, int k, ColumnDataType type) {
+      _type = type;
+      _rows = PinotHipJni.resultAggregationBuffer(res, k, 16).order(ByteOrder.nativeOrder());
+    }
+
+    @Override
+    public Object row(int row) {
+      long time = _rows.getLong(16 * row + 8);
+      switch (_type) {
+        case INT:
+          return new org.apache.pinot.segment.local.customobject.IntLongPair((int) _rows.getLong(16 * row), time);
+        case LONG:
+          return new org.apache.pinot.segment.local.customobject.LongLongPair(_rows.getLong(16 * row), time);
+        case FLOAT:
+          return new org.apache.pinot.segment.local.customobject.FloatLongPair((float) _rows.getDouble(16 * row), time);
+        default:
+          return new org.apache.pinot.segment.local.customobject.DoubleLongPair(_rows.getDouble(16 * row), time);
+      }
     }
   }
 

@@ -144,7 +144,8 @@ JNIEXPORT void JNICALL FN(tableSetColumnType)(JNIEnv* env, jclass c, jlong ctx, 
  *    per aggregation: type, column, log2m, column2, exprOp, percentile bits high, percentile bits low,
  *                     percentileNameForm (the last three zero unless type is PH_AGG_PERCENTILE),
  *    optional: numOrderBy, (kind, index, asc) x numOrderBy, limit, minSegmentGroupTrimSize, skipStarTree,
- *    optional: numHistograms, per HISTOGRAM: aggregation index, equalBins, numEdges, (edge bits high, low) x numEdges]
+ *    optional: numHistograms, per HISTOGRAM: aggregation index, equalBins, numEdges, (edge bits high, low) x numEdges,
+ *    optional: numWithTime, per FIRSTWITHTIME / LASTWITHTIME: aggregation index, declared ph_data_type]
  * decoded into `q`; the arrays it points into are owned by `b` (query_bufs_free).  Returns 0, or -1 for a malformed
  * descriptor (every read is bounds-checked). */
 typedef struct {
@@ -157,11 +158,12 @@ typedef struct {
   const char** vals;
   ph_histogram_args* hist; /* ph_query.histograms: one per aggregation, the HISTOGRAM ones filled */
   double* edges;           /* their edges, back to back */
+  ph_with_time_args* with_time; /* ph_query.with_time: one per aggregation, the with-time ones filled */
 } query_bufs;
 
 static void query_bufs_free(query_bufs* b) {
   free(b->nodes); free(b->preds); free(b->gby); free(b->aggs); free(b->ints); free(b->vals); free(b->order);
-  free(b->hist); free(b->edges);
+  free(b->hist); free(b->edges); free(b->with_time);
 }
 
 static int decode_query(const jint* desc, jsize nd, const char** strs, jsize ns, ph_query* q, query_bufs* b) {
@@ -278,6 +280,20 @@ static int decode_query(const jint* desc, jsize nd, const char** strs, jsize ns,
         }
       }
       q->histograms = b->hist;
+    }
+    if (k < nd) { /* the declared types of the FIRSTWITHTIME / LASTWITHTIME aggregations (ph_query.with_time) */
+      int nw = 0;
+      NEXT(nw);
+      if (nw < 0 || nw > q->num_aggregations) return -1;
+      b->with_time = (ph_with_time_args*)calloc((size_t)q->num_aggregations + 1, sizeof(ph_with_time_args));
+      if (!b->with_time) return -1;
+      for (int i = 0; i < nw; ++i) {
+        int at = 0;
+        NEXT(at);
+        if (at < 0 || at >= q->num_aggregations) return -1;
+        NEXT(b->with_time[at].data_type);
+      }
+      q->with_time = b->with_time;
     }
   }
   /* indices inside the query (children, predicates, root) are range-checked by the library itself */

@@ -41,7 +41,9 @@ const char* const kOptNames[OPT_COUNT] = {
     "part_ring_log2",
     "multi_host_merge",
     "sparse_c",
-    "bins_table_lds_max"
+    "bins_table_lds_max",
+    "withtime_table_lds_max",
+    "withtime_no_combine"
 };
 
 void fail(int code, const std::string& msg) { throw Error{code, msg}; }
@@ -352,6 +354,12 @@ int ph_query_execute(ph_ctx* ctx, const ph_query* query, ph_segment* const* segm
       if (query->min_segment_group_trim_size > 0 && query->num_group_by > 0 && query->num_order_by > 0)
         fail(PH_ERR_UNSUPPORTED, std::string(fn) + " with segment group trim (minSegmentGroupTrimSize)");
     }
+    if (has_with_time_aggregation(query)) {  // their own plan (withtime.cpp): one ordered key per (row, slot), maximised
+      withtime_validate(query);
+      if (ctx->devs.size() > 1) fail(PH_ERR_UNSUPPORTED, "with-time functions on a multi-device context");
+      *out = withtime_execute(&ctx->c, query, segments, num_segments);
+      return;
+    }
     if (has_histogram_aggregation(query)) {  // their own plan (bins.cpp): bin counts over a host-made dictId -> bin table
       bins_validate(query);
       if (ctx->devs.size() > 1) fail(PH_ERR_UNSUPPORTED, "histograms on a multi-device context");
@@ -466,6 +474,10 @@ static Context* dense_device(ph_ctx* ctx, ph_segment* const* segs, int32_t n) {
 }
 
 static void reject_dense_shapes(const ph_query* q) {
+  if (has_with_time_aggregation(q)) {
+    withtime_validate(q);
+    fail(PH_ERR_UNSUPPORTED, "with-time functions on dense partials");
+  }
   if (has_histogram_aggregation(q)) {
     bins_validate(q);
     fail(PH_ERR_UNSUPPORTED, "histograms on dense partials");

@@ -126,14 +126,21 @@ std::string java_double_string(double v) {
   return buf;
 }
 
-std::string agg_column_name(const ph_aggregation& a) {
+const char* column_type_name(int32_t t);
+
+// `declared`: the declared type of a with-time function (ph_with_time_args), unused by the others
+std::string agg_column_name(const ph_aggregation& a, int32_t declared) {
   // (the variance family: getType().getName().toLowerCase(), BaseSingleInputAggregationFunction.java:43-45 over
   // AggregationFunctionType.java:174-181)
   static const char* fn[] = {"count", "sum", "min", "max", "distinctcounthll", "distinctcount", "percentile",
                              "varpop", "varsamp", "stddevpop", "stddevsamp", "covarpop", "covarsamp",
-                             "skewness", "kurtosis", "histogram"};
-  if (a.type < 0 || a.type > PH_AGG_HISTOGRAM) fail(PH_ERR_INVALID_ARGUMENT, "unknown aggregation");
+                             "skewness", "kurtosis", "histogram", "firstwithtime", "lastwithtime"};
+  if (a.type < 0 || a.type > PH_AGG_LASTWITHTIME) fail(PH_ERR_INVALID_ARGUMENT, "unknown aggregation");
   if (a.type == PH_AGG_COUNT) return "count(*)";
+  // getResultColumnName of the subclass (LastIntValueWithTimeAggregationFunction.java:110-116)
+  if (a.type == PH_AGG_FIRSTWITHTIME || a.type == PH_AGG_LASTWITHTIME)
+    return std::string(fn[a.type]) + "(" + (a.column ? a.column : "") + "," + (a.column2 ? a.column2 : "") + ",'" +
+           column_type_name(declared) + "')";
   if (a.type == PH_AGG_COVARPOP || a.type == PH_AGG_COVARSAMP)  // CovarianceAggregationFunction.getResultColumnName
     return std::string(fn[a.type]) + "(" + (a.column ? a.column : "") + "," + (a.column2 ? a.column2 : "") + ")";  // (:72-74)
   if (a.type == PH_AGG_PERCENTILE) {  // PercentileAggregationFunction.getResultColumnName (:60-64)
@@ -180,7 +187,9 @@ std::vector<uint8_t> result_to_datatable(const ph_result* r, const ph_query* q, 
     width[i] = (r->key_types[i] == PH_LONG || r->key_types[i] == PH_DOUBLE) ? 8 : 4;
   }
   for (int k = 0; k < na; ++k) {
-    names.push_back(agg_column_name(q->aggregations[k]));
+    const bool with_time = q->aggregations[k].type == PH_AGG_FIRSTWITHTIME || q->aggregations[k].type == PH_AGG_LASTWITHTIME;
+    if (with_time && !q->with_time) fail(PH_ERR_BAD_QUERY, "with-time function without its declared type");
+    names.push_back(agg_column_name(q->aggregations[k], with_time ? q->with_time[k].data_type : 0));
     // AggregationFunctionUtils.getResultColumnName (:269-275): a filtered function's name carries its FilterContext
     if (q->aggregations[k].filter)
       names.back() += " FILTER(WHERE " + filter_to_string(q, q->aggregations[k].filter - 1) + ")";
@@ -267,6 +276,29 @@ std::vector<uint8_t> result_to_datatable(const ph_result* r, const ph_query* q, 
         put_be(dst + 4, 40u, 4);
         var.i32(34);
         for (uint64_t x : f) var.i64((int64_t)x);
+      } else if (t == PH_AGG_FIRSTWITHTIME || t == PH_AGG_LASTWITHTIME) {
+        // the row's (value, time) pair as {Int,Long,Float,Double}LongPair.toBytes writes it (FloatLongPair.java:39-44),
+        // ObjectType 27 / 28 / 29 / 30 (ObjectSerDeUtils.java:131-134): the value at its own width, the long time
+        const int32_t declared = q->with_time[k].data_type;
+        uint64_t f[2];
+        memcpy(f, base + (size_t)g * 16, 16);
+        const bool narrow = declared == PH_INT || declared == PH_FLOAT;
+        put_be(dst, (uint32_t)var.b.size(), 4);
+        put_be(dst + 4, narrow ? 12u : 16u, 4);
+        var.i32(27 + declared);
+        if (declared == PH_INT) {
+          var.i32((int32_t)(int64_t)f[0]);
+        } else if (declared == PH_FLOAT) {
+          double d;
+          memcpy(&d, &f[0], 8);
+          const float v = (float)d;
+          int32_t bits;
+          memcpy(&bits, &v, 4);
+          var.i32(bits);
+        } else {
+          var.i64((int64_t)f[0]);
+        }
+        var.i64((int64_t)f[1]);
       } else if (t == PH_AGG_HISTOGRAM) {
         // the row's bin counts, the DoubleArrayList the reference's holder keeps (HistogramAggregationFunction.java:
         // 159-171), as ObjectType.DoubleArrayList (ObjectSerDeUtils.java:328-357): int size, the doubles

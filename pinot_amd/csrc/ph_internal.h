@@ -659,6 +659,73 @@ size_t bins_lds_bytes(const BParams& p, int mode);
 void launch_scan_bins(const BParams& p, int mode, bool reg, int grid, hipStream_t s);
 void launch_bins_finish(const BFinishParams& p, hipStream_t s);
 
+// With-time cells (scan_withtime.hip, withtime.cpp): FIRSTWITHTIME / LASTWITHTIME(dataCol, timeCol, 'type').  A slot is
+// one (time column, direction) pair; a result row holds one uint64 cell per slot, the largest key
+//   K = hi_of[dictId(time)] << 32 | (0xFFFFFFFF - ord)
+// of its matched docs.  hi_of is a per-(segment, slot) table the planner makes from the ranks of the (long) time values
+// over the call, flipped for FIRST, never 0; ord numbers the call's docs by segment in call order and, inside a
+// segment, by descending docId, so a larger K is a better time, then an earlier segment, then a larger docId.
+constexpr int kWMaxSlots = 4;     // distinct (time column, direction) pairs of one query
+constexpr int kWMatchRounds = 2;  // rounds of leader matching before the lanes left issue their own atomics
+struct WSegment {
+  int32_t num_docs;
+  uint32_t lo_base;                               // the low key word of doc d is lo_base + d
+  const unsigned long long* mask;                 // the WHERE clause's doc bitmap; nullptr = every doc
+  const uint32_t* gfwd[kMaxGroupCols];            // group-by column g: packed dictIds, their width, dictId -> key id
+  const int32_t* gremap[kMaxGroupCols];           //   (nullptr: identity)
+  int32_t gbits[kMaxGroupCols];
+  const uint32_t* tfwd[kWMaxSlots];               // slot v: packed dictIds of its time column, their width,
+  const uint32_t* hi_of[kWMaxSlots];              //   hi_of[dictId] and the dictionary's entries
+  int32_t tbits[kWMaxSlots];
+  int32_t card[kWMaxSlots];
+};
+struct WParams {
+  const WSegment* segs;
+  const Chunk* chunks;
+  int32_t chunk_begin, chunk_end;
+  int32_t num_slots, num_group_cols;
+  int64_t group_stride[kMaxGroupCols];
+  int64_t num_groups;                             // dense key space (1 without a group-by)
+  int32_t tab_lds;                                // 1: the segments' hi_of tables are staged in LDS, slot s at uint32
+  int32_t tab_off[kWMaxSlots];                    //   tab_off[s] of the staging area (tab_bytes in all, 16-aligned)
+  int32_t tab_bytes;
+  int32_t combine_rounds;                         // kWMatchRounds, or 0 with the wave combine switched off
+  unsigned long long* cells;                      // zeroed [num_groups][num_slots]
+  unsigned long long* n;                          // zeroed [num_groups] matched docs, or nullptr (no COUNT(*))
+  unsigned long long* seg_count;                  // zeroed docs per segment
+};
+// k_withtime_finish: one thread per (row, with-time aggregation) turns the slot's cell into the (value, time) pair
+struct WFinSeg {
+  uint32_t base;                                  // ord of the segment's last doc
+  int32_t num_docs;
+  const uint32_t* dfwd[kMaxAggs];                 // aggregation w: packed dictIds of its data column, their width, the
+  const void* dvals[kMaxAggs];                    //   widened dictionary table (int64 or double) and its entries
+  int32_t dbits[kMaxAggs];
+  int32_t dcard[kMaxAggs];
+  int32_t dkind[kMaxAggs];                        //   and how the tuple's value comes from the table (WT_*)
+};
+enum : int32_t { WT_I64 = 0, WT_F64_OF_I64 = 1, WT_F64 = 2, WT_F64_OF_F32 = 3 };  // tuple value <- dictionary table
+struct WFinAgg {
+  int32_t slot, first;
+  int64_t default_value, default_time;            // the subclass's DEFAULT_VALUE_TIME_PAIR (value as its 8 tuple bytes)
+  const int64_t* time_of_rank;                    // the slot's time column: num_times distinct (long) values, ascending
+  int64_t num_times;
+  int64_t* out;                                   // [num_groups] pairs {value bits, time}
+};
+struct WFinishParams {
+  int64_t num_groups;
+  int32_t num_aggs, num_slots, num_segs;
+  int32_t write_n;                                // 1: no COUNT(*) ran, n[g] becomes "slot 0's cell holds a doc"
+  const unsigned long long* cells;
+  unsigned long long* n;
+  const WFinSeg* segs;
+  const WFinAgg* aggs;
+};
+size_t withtime_lds_bytes(const WParams& p, int mode);
+// `reg`: MODE_AGG's register-direct decode (every slot's packed time width is at most 16 bits)
+void launch_scan_withtime(const WParams& p, int mode, bool reg, int grid, hipStream_t s);
+void launch_withtime_finish(const WFinishParams& p, hipStream_t s);
+
 // Kernel B of the partitioned group-by: aggregates one batch of records per partition in LDS, then merges
 // the partition's key range into the dense result table (each key range has exactly one owner block).
 struct PartAggParams {
@@ -931,6 +998,8 @@ enum Opt : int {
   OPT_MULTI_HOST_MERGE,
   OPT_SPARSE_C,
   OPT_BINS_TABLE_LDS_MAX,
+  OPT_WITHTIME_TABLE_LDS_MAX,
+  OPT_WITHTIME_NO_COMBINE,
   OPT_COUNT
 };
 constexpr int64_t kOptUnset = INT64_MIN;
@@ -1328,6 +1397,11 @@ ph_result* bins_execute(Context* ctx, const ph_query* q, ph_segment* const* segs
 // getBinId of `count` values of a stored type (host order) into out[i], -1 for a value outside every bin
 void histogram_bin_ids(const double* edges, int32_t num_edges, int32_t equal_bins, int32_t data_type, const void* values,
                        int64_t count, int32_t* out);
+// with-time cells (withtime.cpp): a FIRSTWITHTIME / LASTWITHTIME somewhere in the query
+inline bool is_with_time(int32_t t) { return t == PH_AGG_FIRSTWITHTIME || t == PH_AGG_LASTWITHTIME; }
+bool has_with_time_aggregation(const ph_query* q);
+void withtime_validate(const ph_query* q);  // host-only argument and shape checks of such a query
+ph_result* withtime_execute(Context* ctx, const ph_query* q, ph_segment* const* segs, int32_t nseg);
 // FilterContext.toString of the tree rooted at `root` (FilterContext.java:94-114 and each Predicate.toString)
 std::string filter_to_string(const ph_query* q, int32_t root);
 ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const* segs, int32_t nseg,

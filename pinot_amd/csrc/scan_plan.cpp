@@ -125,6 +125,7 @@ WhereBitmap where_bitmap(Context* ctx, const ph_query* q, int32_t root, ph_segme
   qc.min_segment_group_trim_size = -1;
   qc.skip_star_tree = 1;
   qc.histograms = nullptr;
+  qc.with_time = nullptr;
   const int64_t off[1] = {0};
   FilterDocset fd{b.words, off, need};
   DenseArgs d{0, nullptr, 0, 0, nullptr};

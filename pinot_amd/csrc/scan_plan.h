@@ -1,5 +1,6 @@
 // scan_plan.h -- the host-side steps that the bitmap-then-scan plans share: filtered aggregations (filtered.cpp), the
-// variance family (moments.cpp), COVAR (comoments.cpp), SKEWNESS / KURTOSIS (moments4.cpp) and HISTOGRAM (bins.cpp).  Each of those planners
+// variance family (moments.cpp), COVAR (comoments.cpp), SKEWNESS / KURTOSIS (moments4.cpp), HISTOGRAM (bins.cpp) and
+// FIRSTWITHTIME / LASTWITHTIME (withtime.cpp).  Each of those planners
 // reads top to bottom as a list of steps; the steps that are the same in all of them live here (scan_plan.cpp), once:
 // the call checks, the range of an argument column, the WHERE clause's class and doc bitmap per segment, the dense key
 // space with its refusals and the mode rule, a segment's group-by streams and chunks, and the assembly of the result.

@@ -20,7 +20,8 @@ from typing import Any, Dict, List, Sequence
 import numpy as np
 
 from .query import (COUNT, COVARIANCE_AGGREGATIONS, DISTINCTCOUNT, DISTINCTCOUNTHLL, FOURTHMOMENT_AGGREGATIONS,
-                    HISTOGRAM, MAX, MIN, PERCENTILE, SUM, VARIANCE_AGGREGATIONS, QueryContext)
+                    FIRSTWITHTIME, HISTOGRAM, MAX, MIN, PERCENTILE, SUM, VARIANCE_AGGREGATIONS, WITHTIME_AGGREGATIONS,
+                    QueryContext)
 from .reduce import ResultTable, ValueCounts, merge_intermediate, reduce_groups
 
 # MetadataKey id -> (name, value type) (DataTable.java:103-137); "I" int, "L" long, "S" string
@@ -45,6 +46,10 @@ DOUBLE_LIST_OBJECT_TYPE = 3  # ObjectSerDeUtils.ObjectType.DoubleArrayList: PERC
 VARIANCE_TUPLE_OBJECT_TYPE = 33  # ObjectSerDeUtils.ObjectType.VarianceTuple (ObjectSerDeUtils.java:137)
 COVARIANCE_TUPLE_OBJECT_TYPE = 32  # ObjectSerDeUtils.ObjectType.CovarianceTuple (ObjectSerDeUtils.java:136)
 FOURTHMOMENT_OBJECT_TYPE = 34  # ObjectSerDeUtils.ObjectType.PinotFourthMoment (ObjectSerDeUtils.java:138)
+# the (value, time) pairs of FIRSTWITHTIME / LASTWITHTIME by declared type: IntLongPair, LongLongPair, FloatLongPair,
+# DoubleLongPair (ObjectSerDeUtils.java:131-134) and the struct format of their toBytes (FloatLongPair.java:39-44)
+PAIR_OBJECT_TYPES = {27: "INT", 28: "LONG", 29: "FLOAT", 30: "DOUBLE"}
+_PAIR_FORMAT = {"INT": ">iq", "LONG": ">qq", "FLOAT": ">fq", "DOUBLE": ">dq"}
 
 
 @dataclass
@@ -160,6 +165,19 @@ def fourthmoment_deserialize(b: bytes) -> tuple:
     return struct.unpack(">qdddd", b)
 
 
+def pair_serialize(data_type: str, pair: tuple) -> bytes:
+    """{Int,Long,Float,Double}LongPair.toBytes: the value at its own width, then the 8-byte time, big-endian."""
+    return struct.pack(_PAIR_FORMAT[data_type], *pair)
+
+
+def pair_deserialize(otype: int, b: bytes) -> tuple:
+    """A (value, time) pair from the bytes of object type 27 / 28 / 29 / 30."""
+    fmt = _PAIR_FORMAT[PAIR_OBJECT_TYPES[otype]]
+    if len(b) != struct.calcsize(fmt):
+        raise ValueError(f"{PAIR_OBJECT_TYPES[otype]}LongPair of {len(b)} bytes")
+    return struct.unpack(fmt, b)
+
+
 def decode(buf: bytes) -> DataTable:
     r = _Reader(buf)
     version = r.i32()
@@ -227,6 +245,13 @@ def decode(buf: bytes) -> DataTable:
     return DataTable(names, types, rows, md, exceptions, len(var), spans)
 
 
+def with_time_default(a) -> tuple:
+    """DEFAULT_VALUE_TIME_PAIR of the subclass (Last|First{Int,Long,Float,Double}ValueWithTimeAggregationFunction.java:
+    42-44)."""
+    value = {"INT": -(1 << 31), "LONG": -(1 << 63)}.get(a.data_type, float("nan"))
+    return value, (1 << 63) - 1 if a.function == FIRSTWITHTIME else -(1 << 63)
+
+
 def _merge(fn, a, b):
     return merge_intermediate(fn, a, b)
 
@@ -255,6 +280,10 @@ def reduce_datatables(q: QueryContext, tables: Sequence[DataTable]) -> ResultTab
                     otype, payload = v
                     assert otype == DOUBLE_LIST_OBJECT_TYPE
                     v = histogram_deserialize(payload)
+                elif a.function in WITHTIME_AGGREGATIONS:
+                    otype, payload = v
+                    assert PAIR_OBJECT_TYPES.get(otype) == a.data_type
+                    v = pair_deserialize(otype, payload)
                 elif a.function in VARIANCE_AGGREGATIONS:
                     otype, payload = v
                     assert otype == VARIANCE_TUPLE_OBJECT_TYPE
@@ -276,6 +305,8 @@ def reduce_datatables(q: QueryContext, tables: Sequence[DataTable]) -> ResultTab
         empty = {f: (0, 0.0, 0.0) for f in VARIANCE_AGGREGATIONS}
         empty.update({f: (0.0, 0.0, 0.0, 0) for f in COVARIANCE_AGGREGATIONS}, COUNT=0)
         empty.update({f: (0,) + (float("nan"),) * 4 for f in FOURTHMOMENT_AGGREGATIONS})
-        groups[()] = [(0.0,) * a.num_bins if a.function == HISTOGRAM else empty.get(a.function) for a in q.aggregations]
+        groups[()] = [(0.0,) * a.num_bins if a.function == HISTOGRAM else
+                      with_time_default(a) if a.function in WITHTIME_AGGREGATIONS else empty.get(a.function)
+                      for a in q.aggregations]
     keys = list(groups)
     return reduce_groups(q, keys, [groups[k] for k in keys])

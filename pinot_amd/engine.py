@@ -20,7 +20,8 @@ import numpy as np
 from . import native as N
 from .query import (COUNT, COVARIANCE_AGGREGATIONS, COVARPOP, COVARSAMP, DISTINCTCOUNT, DISTINCTCOUNTHLL,
                     FOURTHMOMENT_AGGREGATIONS, HISTOGRAM, KURTOSIS, MAX, MIN, PERCENTILE, SKEWNESS, STDDEVPOP, STDDEVSAMP, SUM,
-                    VARIANCE_AGGREGATIONS, VARPOP, VARSAMP, FilterContext, QueryContext, parse_sql)
+                    VARIANCE_AGGREGATIONS, VARPOP, VARSAMP, FIRSTWITHTIME, LASTWITHTIME, WITHTIME_AGGREGATIONS,
+                    FilterContext, QueryContext, parse_sql)
 from .reduce import ResultTable, ValueCounts, reduce_groups
 from .segment import PinnedSegment, SegmentBuffers
 
@@ -29,7 +30,7 @@ _AGG = {COUNT: N.PH_AGG_COUNT, SUM: N.PH_AGG_SUM, MIN: N.PH_AGG_MIN, MAX: N.PH_A
         PERCENTILE: N.PH_AGG_PERCENTILE, VARPOP: N.PH_AGG_VARPOP, VARSAMP: N.PH_AGG_VARSAMP,
         STDDEVPOP: N.PH_AGG_STDDEVPOP, STDDEVSAMP: N.PH_AGG_STDDEVSAMP, COVARPOP: N.PH_AGG_COVARPOP,
         COVARSAMP: N.PH_AGG_COVARSAMP, SKEWNESS: N.PH_AGG_SKEWNESS, KURTOSIS: N.PH_AGG_KURTOSIS,
-        HISTOGRAM: N.PH_AGG_HISTOGRAM}
+        HISTOGRAM: N.PH_AGG_HISTOGRAM, FIRSTWITHTIME: N.PH_AGG_FIRSTWITHTIME, LASTWITHTIME: N.PH_AGG_LASTWITHTIME}
 _PRED = {"EQ": N.PH_PRED_EQ, "NOT_EQ": N.PH_PRED_NOT_EQ, "IN": N.PH_PRED_IN, "NOT_IN": N.PH_PRED_NOT_IN,
          "RANGE": N.PH_PRED_RANGE}
 
@@ -66,7 +67,7 @@ SCAN_KERNEL_NAMES = {0: "none", 1: "k_scan", 2: "k_agg_lean", 3: "k_agg_sparse",
                      18: "k_scan, PERCENTILE histograms in LDS", 19: "k_scan, PERCENTILE histograms in HBM",
                      20: "k_scan_filtered", 21: "k_scan_moments + k_moments_finish",
                      22: "k_scan_comoments + k_comoments_finish", 23: "k_scan_moments4 + k_moments4_finish",
-                     24: "k_scan_bins + k_bins_finish"}
+                     24: "k_scan_bins + k_bins_finish", 25: "k_scan_withtime + k_withtime_finish"}
 
 
 @dataclass
@@ -113,7 +114,7 @@ class IntermediateResult:
     # per aggregation: int64 (COUNT), float64 (SUM/MIN/MAX), uint8[n, m] (HLL), DistinctColumn (DISTINCTCOUNT),
     # HistogramColumn (PERCENTILE), VARIANCE_TUPLE_DTYPE records (VARPOP / VARSAMP / STDDEVPOP / STDDEVSAMP),
     # COVARIANCE_TUPLE_DTYPE records (COVARPOP / COVARSAMP), FOURTHMOMENT_TUPLE_DTYPE records (SKEWNESS / KURTOSIS),
-    # float64[n, B] bin counts (HISTOGRAM)
+    # float64[n, B] bin counts (HISTOGRAM), WITHTIME_INT_DTYPE / WITHTIME_REAL_DTYPE records (FIRSTWITHTIME / LASTWITHTIME)
     agg_columns: List[object]
     num_groups: int
     functions: List[str]
@@ -141,8 +142,8 @@ class IntermediateResult:
                 conv.append([col.value_counts(i) for i in range(self.num_groups)])
             elif f == HISTOGRAM:  # the row's B bin counts
                 conv.append([tuple(t) for t in col.tolist()])
-            elif f in VARIANCE_AGGREGATIONS + COVARIANCE_AGGREGATIONS + FOURTHMOMENT_AGGREGATIONS:
-                # (count, sum, m2) / (sum_x, sum_y, sum_xy, count) / (n, m1, m2, m3, m4)
+            elif f in VARIANCE_AGGREGATIONS + COVARIANCE_AGGREGATIONS + FOURTHMOMENT_AGGREGATIONS + WITHTIME_AGGREGATIONS:
+                # (count, sum, m2) / (sum_x, sum_y, sum_xy, count) / (n, m1, m2, m3, m4) / (value, time)
                 conv.append([tuple(t) for t in col.tolist()])
             else:
                 conv.append(col.tolist())
@@ -233,7 +234,17 @@ class _QueryStruct:
                     edges = (ctypes.c_double * len(a.edges))(*a.edges)
                     self.keep.append(edges)
                     hist_arr[k] = N.HistogramArgs(edges, len(a.edges), a.equal_bins)
-        self.keep += [node_arr, pred_arr, gb, agg_arr, hist_arr]
+        # the declared types of the FIRSTWITHTIME / LASTWITHTIME aggregations, one ph_with_time_args per aggregation
+        wt_arr = None
+        if any(a.function in WITHTIME_AGGREGATIONS for a in q.aggregations):
+            wt_arr = (N.WithTimeArgs * len(q.aggregations))()
+            for k, a in enumerate(q.aggregations):
+                if a.function in WITHTIME_AGGREGATIONS:
+                    if a.data_type not in N.DATA_TYPES:  # BOOLEAN: no ph_data_type code; the CPU plan serves it
+                        raise N.UnsupportedError(N.PH_ERR_UNSUPPORTED,
+                                                 f"with-time function with declared type {a.data_type}")
+                    wt_arr[k] = N.WithTimeArgs(N.DATA_TYPES[a.data_type])
+        self.keep += [node_arr, pred_arr, gb, agg_arr, hist_arr, wt_arr]
         end_ms = 0
         if "timeoutMs" in q.options:
             import time
@@ -251,7 +262,7 @@ class _QueryStruct:
                               len(q.aggregations), aggs, q.num_groups_limit, end_ms,
                               ctypes.pointer(interrupt) if interrupt is not None else None,
                               len(obs), ob_arr, int(q.limit), seg_trim,
-                              int(str(q.options.get("skipStarTree", "false")).lower() == "true"), hist_arr)
+                              int(str(q.options.get("skipStarTree", "false")).lower() == "true"), hist_arr, wt_arr)
 
 
 # a variance function's result row: the reference's VarianceTuple (VarianceTuple.java:25-33) in host order
@@ -262,6 +273,10 @@ COVARIANCE_TUPLE_DTYPE = np.dtype([("sum_x", np.float64), ("sum_y", np.float64),
 # a SKEWNESS / KURTOSIS result row: the reference's PinotFourthMoment in host order
 FOURTHMOMENT_TUPLE_DTYPE = np.dtype([("n", np.int64), ("m1", np.float64), ("m2", np.float64), ("m3", np.float64),
                                      ("m4", np.float64)])
+# a FIRSTWITHTIME / LASTWITHTIME result row: the reference's ValueLongPair in host order, the value int64 for a declared
+# INT / LONG and float64 for FLOAT / DOUBLE
+WITHTIME_INT_DTYPE = np.dtype([("value", np.int64), ("time", np.int64)])
+WITHTIME_REAL_DTYPE = np.dtype([("value", np.float64), ("time", np.int64)])
 _KEY_DTYPE = {N.PH_INT: np.int32, N.PH_LONG: np.int64, N.PH_FLOAT: np.float32, N.PH_DOUBLE: np.float64}
 
 
@@ -292,7 +307,7 @@ OPTION_NAMES = ("roaring_atomic", "agg_cont", "group_cont", "disable_partition",
                 "lds_generic", "count_generic", "lds_lean", "group_reg_lg", "stat_fuse", "interrupt_chunks",
                 "part_klo", "part_batch_rows", "part_flush_first", "part_depth", "part_lds", "part_sets",
                 "part_wg_per_cu", "part_slices", "part_mm_blind", "part_serial", "part_ring_log2", "multi_host_merge",
-                "sparse_c", "bins_table_lds_max")
+                "sparse_c", "bins_table_lds_max", "withtime_table_lds_max", "withtime_no_combine")
 OPTION_UNSET = -(1 << 63)
 
 
@@ -488,6 +503,9 @@ class GpuContext:
                 arr = HistogramColumn(hist[:, :d], values, finals)
             elif a.function == HISTOGRAM:
                 arr = view(L.ph_result_aggregation_data(r, k), 8 * a.num_bins * n).view(np.float64).reshape(n, a.num_bins)
+            elif a.function in WITHTIME_AGGREGATIONS:
+                arr = view(L.ph_result_aggregation_data(r, k), 16 * n).view(
+                    WITHTIME_INT_DTYPE if a.data_type in ("INT", "LONG") else WITHTIME_REAL_DTYPE)
             elif a.function in VARIANCE_AGGREGATIONS:
                 arr = view(L.ph_result_aggregation_data(r, k), 24 * n).view(VARIANCE_TUPLE_DTYPE)
             elif a.function in COVARIANCE_AGGREGATIONS:

@@ -26,7 +26,8 @@ PH_PRED_EQ, PH_PRED_NOT_EQ, PH_PRED_IN, PH_PRED_NOT_IN, PH_PRED_RANGE = range(5)
 PH_FILTER_AND, PH_FILTER_OR, PH_FILTER_NOT, PH_FILTER_PREDICATE = range(4)
 (PH_AGG_COUNT, PH_AGG_SUM, PH_AGG_MIN, PH_AGG_MAX, PH_AGG_DISTINCTCOUNTHLL, PH_AGG_DISTINCTCOUNT,
  PH_AGG_PERCENTILE, PH_AGG_VARPOP, PH_AGG_VARSAMP, PH_AGG_STDDEVPOP, PH_AGG_STDDEVSAMP, PH_AGG_COVARPOP,
- PH_AGG_COVARSAMP, PH_AGG_SKEWNESS, PH_AGG_KURTOSIS, PH_AGG_HISTOGRAM) = range(16)
+ PH_AGG_COVARSAMP, PH_AGG_SKEWNESS, PH_AGG_KURTOSIS, PH_AGG_HISTOGRAM, PH_AGG_FIRSTWITHTIME,
+ PH_AGG_LASTWITHTIME) = range(18)
 
 
 class PinotHipError(RuntimeError):
@@ -103,12 +104,19 @@ PH_KERNEL_SCAN_MOMENTS = 21
 PH_KERNEL_SCAN_COMOMENTS = 22
 PH_KERNEL_SCAN_MOMENTS4 = 23
 PH_KERNEL_SCAN_BINS = 24
+PH_KERNEL_SCAN_WITHTIME = 25
 
 
 class HistogramArgs(ctypes.Structure):
     """ph_histogram_args: entry k of ph_query.histograms holds the bin edges of aggregation k when it is a HISTOGRAM."""
     _fields_ = [("hist_edges", ctypes.POINTER(ctypes.c_double)), ("hist_num_edges", ctypes.c_int32),
                 ("hist_equal_bins", ctypes.c_int32)]
+
+
+class WithTimeArgs(ctypes.Structure):
+    """ph_with_time_args: entry k of ph_query.with_time holds the declared type of aggregation k when it is a
+    FIRSTWITHTIME / LASTWITHTIME."""
+    _fields_ = [("data_type", ctypes.c_int32)]
 
 
 class OrderBy(ctypes.Structure):
@@ -127,7 +135,7 @@ class Query(ctypes.Structure):
                 ("end_time_ms", ctypes.c_int64), ("interrupt", ctypes.POINTER(ctypes.c_int32)),
                 ("num_order_by", ctypes.c_int32), ("order_by", ctypes.POINTER(OrderBy)), ("limit", ctypes.c_int32),
                 ("min_segment_group_trim_size", ctypes.c_int32), ("skip_star_tree", ctypes.c_int32),
-                ("histograms", ctypes.POINTER(HistogramArgs))]
+                ("histograms", ctypes.POINTER(HistogramArgs)), ("with_time", ctypes.POINTER(WithTimeArgs))]
 
 
 PH_MAX_DENSE_TABLES = 16

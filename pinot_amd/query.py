@@ -44,6 +44,11 @@ FOURTHMOMENT_AGGREGATIONS = (SKEWNESS, KURTOSIS)
 # HISTOGRAM(col, lower, upper, numBins) / HISTOGRAM(col, ARRAY[e0, ..., eB]) (HistogramAggregationFunction.java:52-84): a
 # DoubleArrayList of B bin counts per result holder
 HISTOGRAM = "HISTOGRAM"
+# FIRSTWITHTIME / LASTWITHTIME(dataCol, timeCol, 'type') (AggregationFunctionFactory.java:201-254): a (value, time) pair
+# per result holder, the value of the doc with the smallest / largest time
+FIRSTWITHTIME, LASTWITHTIME = "FIRSTWITHTIME", "LASTWITHTIME"
+WITHTIME_AGGREGATIONS = (FIRSTWITHTIME, LASTWITHTIME)
+WITHTIME_DATA_TYPES = ("BOOLEAN", "INT", "LONG", "FLOAT", "DOUBLE", "STRING")  # the factory's switch (:212-228)
 SUPPORTED_AGGREGATIONS = ((COUNT, SUM, MIN, MAX, DISTINCTCOUNTHLL, DISTINCTCOUNT, PERCENTILE) + VARIANCE_AGGREGATIONS
                           + COVARIANCE_AGGREGATIONS + FOURTHMOMENT_AGGREGATIONS)
 DEFAULT_HLL_LOG2M = 8  # CommonConstants.Helix.DEFAULT_HYPERLOGLOG_LOG2M (CommonConstants.java:96-97)
@@ -210,6 +215,8 @@ class AggregationSpec:
     # HISTOGRAM: the B + 1 edges of the ARRAY form (equal_bins 0), or (lower, upper) with equal_bins = B
     edges: Tuple[float, ...] = ()
     equal_bins: int = 0
+    # FIRSTWITHTIME / LASTWITHTIME: the declared type, upper case (column2 is the time column)
+    data_type: Optional[str] = None
 
     @property
     def num_bins(self) -> int:
@@ -223,6 +230,8 @@ class AggregationSpec:
             from dataclasses import replace
             return f"{replace(self, filter=None).result_name()} FILTER(WHERE {self.filter.to_string()})"
         arg = "*" if self.column is None else self.column
+        if self.function in WITHTIME_AGGREGATIONS:  # LastIntValueWithTimeAggregationFunction.getResultColumnName (:110-116)
+            return f"{self.function.lower()}({self.column},{self.column2},'{self.data_type}')"
         if self.op:
             arg = f"{EXPR_OPS[self.op]}({self.column},{self.column2})"
         elif self.function in COVARIANCE_AGGREGATIONS:  # no space after the comma (getResultColumnName :72-74)
@@ -414,11 +423,49 @@ class _Parser:
             raise SqlParseError(f"The number of bins must be greater than zero, given {bins}")
         return AggregationSpec(HISTOGRAM, col, edges=(lower, upper), equal_bins=int(bins))
 
+    def with_time_call(self, fn: str) -> AggregationSpec:
+        """FIRSTWITHTIME / LASTWITHTIME(dataCol, timeCol, 'type') with the factory's argument checks
+        (AggregationFunctionFactory.java:201-254)."""
+        name = f"{fn[:-8]}_WITH_TIME"
+        usage = f"The function can be used as {fn[:-8].lower()}WithTime(dataColumn, timeColumn, 'dataType')"
+        args, depth = [[]], 0  # the argument list as token runs, split at the top-level commas
+        while True:
+            t = self.take()
+            if t[0] == "eof":
+                raise SqlParseError(f"expected ), got {t}")
+            if t == ("op", ")") and depth == 0:
+                break
+            depth += (t == ("op", "(")) - (t == ("op", ")"))
+            if t == ("op", ",") and depth == 0:
+                args.append([])
+            else:
+                args[-1].append(t)
+        count = len(args) if args != [[]] else 0
+        if count != 3:
+            raise SqlParseError(f"{name} expects 3 arguments, got: {count}. {usage}")
+        if len(args[2]) != 1 or args[2][0][0] not in ("str", "num"):
+            kind = "IDENTIFIER" if len(args[2]) == 1 else "FUNCTION"
+            raise SqlParseError(f"{name} expects the 3rd argument to be literal, got: {kind}. {usage}")
+        data_type = args[2][0][1].strip("'").upper()
+        if data_type not in WITHTIME_DATA_TYPES:  # DataType.valueOf fails, or the switch's default
+            raise SqlParseError(f"Unsupported data type for {name}: {data_type}")
+        cols = []
+        for a in args[:2]:
+            if len(a) != 1 or a[0][0] != "id":
+                raise SqlParseError(f"{name} over an expression argument is not supported: expected a column")
+            cols.append(a[0][1])
+        return AggregationSpec(fn, cols[0], column2=cols[1], data_type=data_type)
+
     def plain_agg_call(self) -> Optional[AggregationSpec]:
         t, n = self.peek(), self.peek(1)
         if t[0] == "id" and t[1].upper() == HISTOGRAM and n == ("op", "("):
             self.i += 2
             return self.histogram_call()
+        # every spelling the reference's canonicalisation accepts: underscores removed, case ignored
+        # (AggregationFunctionType.getNormalizedAggregationFunctionName, AggregationFunctionType.java:424-426)
+        if t[0] == "id" and n == ("op", "(") and t[1].upper().replace("_", "").replace("$", "") in WITHTIME_AGGREGATIONS:
+            self.i += 2
+            return self.with_time_call(t[1].upper().replace("_", "").replace("$", ""))
         pm = re.fullmatch(r"PERCENTILE(\d*)", t[1].upper()) if t[0] == "id" and n == ("op", "(") else None
         if pm:  # PERCENTILE(col, p) | PERCENTILEnn(col)  (AggregationFunctionFactory.java:72-128)
             self.i += 2

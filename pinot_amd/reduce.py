@@ -30,8 +30,8 @@ from typing import Any, List, Sequence
 import numpy as np
 
 from .query import (COUNT, COVARIANCE_AGGREGATIONS, COVARSAMP, DISTINCTCOUNT, DISTINCTCOUNTHLL,
-                    FOURTHMOMENT_AGGREGATIONS, HISTOGRAM, MAX, MIN, PERCENTILE, SKEWNESS, STDDEVPOP, STDDEVSAMP, SUM,
-                    VARIANCE_AGGREGATIONS, VARSAMP, QueryContext)
+                    FIRSTWITHTIME, FOURTHMOMENT_AGGREGATIONS, HISTOGRAM, LASTWITHTIME, MAX, MIN, PERCENTILE, SKEWNESS,
+                    STDDEVPOP, STDDEVSAMP, SUM, VARIANCE_AGGREGATIONS, VARSAMP, WITHTIME_AGGREGATIONS, QueryContext)
 
 
 def _java_round(x: float) -> int:
@@ -279,6 +279,12 @@ def merge_intermediate(function: str, a, b):
         return a.merge(b)
     if function == HISTOGRAM:  # DoubleVectorOpUtils.vectorAdd (HistogramAggregationFunction.merge :174-177)
         return tuple(float(x) + float(y) for x, y in zip(a, b))
+    # (value, time) pairs: the first argument is kept on equal times (LastWithTimeAggregationFunction.merge :200-206,
+    # FirstWithTimeAggregationFunction.merge :199-205)
+    if function == LASTWITHTIME:
+        return a if a[1] >= b[1] else b
+    if function == FIRSTWITHTIME:
+        return a if a[1] <= b[1] else b
     if function in VARIANCE_AGGREGATIONS:
         return variance_merge(a, b)
     if function in COVARIANCE_AGGREGATIONS:
@@ -308,6 +314,8 @@ def final_value(spec, value):
         return percentile_final(value, spec.percentile)
     if spec.function == HISTOGRAM:  # DOUBLE_ARRAY: the list of doubles (extractFinalResult returns the list)
         return [float(x) for x in value]
+    if spec.function in WITHTIME_AGGREGATIONS:  # extractFinalResult: the pair's value, in the declared type
+        return int(value[0]) if spec.data_type in ("INT", "LONG") else float(value[0])
     if spec.function in VARIANCE_AGGREGATIONS:
         return variance_final(value, spec.function)
     if spec.function in COVARIANCE_AGGREGATIONS:
