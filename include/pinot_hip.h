@@ -122,13 +122,27 @@ typedef struct {
 } ph_segment_desc;
 
 /* ------------------------------------------------------------------ query description */
-typedef enum { PH_PRED_EQ = 0, PH_PRED_NOT_EQ = 1, PH_PRED_IN = 2, PH_PRED_NOT_IN = 3, PH_PRED_RANGE = 4 }
-    ph_predicate_type;
+/* PH_PRED_LIKE: `column LIKE values[0]` (num_values == 1; a missing pattern is PH_ERR_BAD_QUERY) on a STRING column.
+ * The reference rewrites LIKE to REGEXP_LIKE (RegexpPatternConverterUtils.likeToRegexpLike :43-131: `%` any run, `_` any
+ * one code point, `\_` and `\%` literals, a `\` before another character or at the end a literal backslash, runs of `%`
+ * at either end dropping that side's anchor) and evaluates java.util.regex's find() on every dictionary value
+ * (RegexpLikePredicateEvaluatorFactory.java:79-81), so neither wildcard crosses a line terminator (\n, \r, U+0085, U+2028,
+ * U+2029) and an end-anchored pattern also matches before one final line terminator.  Here a kernel matches every entry
+ * of the pinned dictionary (there is no host evaluator) and the leaf scans the matching dictIds: without an FST index a
+ * REGEXP_LIKE leaf is a ScanBasedFilterOperator on sorted and inverted columns too (FilterOperatorUtils.java:105-112),
+ * for the AND order and for num_entries_scanned_in_filter.  NOT LIKE is PH_FILTER_NOT over it.  PH_ERR_UNSUPPORTED, each
+ * with its own message (the caller's CPU plan serves them): a non-STRING column; a pattern of more than 8 runs between
+ * `%`, more than 128 bytes, or more than 64 bytes in one run; a pattern that holds a line terminator, or a backslash
+ * before a regex metacharacter (where the reference's regex is not the literal); dictionary entries wider than 256
+ * bytes.  A query holding a LIKE is not answered from a star-tree: it scans the segment's own docs. */
+typedef enum {
+  PH_PRED_EQ = 0, PH_PRED_NOT_EQ = 1, PH_PRED_IN = 2, PH_PRED_NOT_IN = 3, PH_PRED_RANGE = 4, PH_PRED_LIKE = 5
+} ph_predicate_type;
 
 typedef struct {
   int32_t type;                 /* ph_predicate_type */
   const char* column;
-  int32_t num_values;           /* EQ / NOT_EQ: 1; IN / NOT_IN: n */
+  int32_t num_values;           /* EQ / NOT_EQ: 1; IN / NOT_IN: n; LIKE: 1 (the pattern) */
   const char* const* values;    /* literals as strings, as Pinot's Predicate keeps them */
   const char* lower;            /* RANGE bounds; "*" = RangePredicate.UNBOUNDED */
   const char* upper;

@@ -14,6 +14,8 @@ import org.apache.pinot.common.request.context.predicate.NotEqPredicate;
 import org.apache.pinot.common.request.context.predicate.NotInPredicate;
 import org.apache.pinot.common.request.context.predicate.Predicate;
 import org.apache.pinot.common.request.context.predicate.RangePredicate;
+import org.apache.pinot.common.request.context.predicate.RegexpLikePredicate;
+import org.apache.pinot.common.utils.RegexpPatternConverterUtils;
 import org.apache.pinot.core.query.aggregation.function.AggregationFunction;
 import org.apache.pinot.core.query.aggregation.function.DistinctCountHLLAggregationFunction;
 import org.apache.pinot.core.query.request.context.QueryContext;
@@ -27,7 +29,7 @@ import org.apache.pinot.segment.spi.AggregationFunctionType;
  * null handling, non-identifier group-by expressions, aggregations other than
  * COUNT / SUM / MIN / MAX / DISTINCTCOUNTHLL / DISTINCTCOUNT / PERCENTILE (over a column; SUM / MIN / MAX also over a 2-operand
  * mult/sub/add), predicates other than
- * EQ / NOT_EQ / IN / NOT_IN / RANGE on identifiers, and a segment group trim (GroupByOperator.java:114-130) ordered
+ * EQ / NOT_EQ / IN / NOT_IN / RANGE / a rewritten LIKE on identifiers, and a segment group trim (GroupByOperator.java:114-130) ordered
  * by anything but group-by columns and aggregations.
  */
 public final class GpuQuery {
@@ -280,6 +282,54 @@ public final class GpuQuery {
       }
     }
 
+    // The LIKE pattern whose rewrite (RegexpPatternConverterUtils.likeToRegexpLike) is `regex`: `.*` -> %, `.` -> _,
+    // an escaped character -> itself (\_ and \% stay escaped); checked by converting the candidate back, so any other
+    // regex is refused and keeps the CPU plan
+    static String likePatternOf(String regex) {
+      StringBuilder sb = new StringBuilder();
+      int i = 0;
+      int end = regex.length();
+      if (regex.isEmpty()) {
+        return "%";
+      }
+      if (regex.charAt(0) == '^') {
+        i = 1;
+      } else {
+        sb.append('%');
+      }
+      boolean anchoredEnd = end > i && regex.charAt(end - 1) == '$' && (end - 2 < i || regex.charAt(end - 2) != '\\');
+      if (anchoredEnd) {
+        end--;
+      }
+      while (i < end) {
+        char c = regex.charAt(i++);
+        if (c == '.') {
+          if (i < end && regex.charAt(i) == '*') {
+            sb.append('%');
+            i++;
+          } else {
+            sb.append('_');
+          }
+        } else if (c == '\\' && i < end) {
+          char x = regex.charAt(i++);
+          if (x == '_' || x == '%') {
+            sb.append('\\');
+          }
+          sb.append(x);
+        } else {
+          sb.append(c);
+        }
+      }
+      if (!anchoredEnd) {
+        sb.append('%');
+      }
+      String like = sb.toString();
+      if (!RegexpPatternConverterUtils.likeToRegexpLike(like).equals(regex)) {
+        throw new UnsupportedOperationException("REGEXP_LIKE that is no LIKE rewrite");
+      }
+      return like;
+    }
+
     // Predicate (pinot-common request/context/predicate) -> ph_predicate: values stay strings, as Pinot keeps them
     int predicate(Predicate p) {
       ExpressionContext lhs = p.getLhs();
@@ -318,6 +368,12 @@ public final class GpuQuery {
           upperInc = r.isUpperInclusive() ? 1 : 0;
           break;
         }
+        case REGEXP_LIKE:
+          // a LIKE reaches the server rewritten (RequestContextUtils: likeToRegexpLike); the library takes the LIKE
+          // pattern itself, so only a regex that is such a rewrite goes to the GPU
+          type = PinotHipJni.PRED_LIKE;
+          values.add(likePatternOf(((RegexpLikePredicate) p).getValue()));
+          break;
         default:
           throw new UnsupportedOperationException(p.getType().toString());
       }

@@ -91,6 +91,37 @@ bool has_filtered_aggregation(const ph_query* q) {
   return false;
 }
 
+// RegexpPatternConverterUtils.likeToRegexpLike (:43-131): the regex text a LIKE pattern is rewritten to
+std::string like_to_regexp(const std::string& p) {
+  if (p.empty()) return "^$";
+  size_t start = 0, end = p.size();
+  std::string out = "^", suffix = "$";
+  if (p[0] == '%') {
+    start = p.find_first_not_of('%');
+    if (start == std::string::npos) return "";
+    out.clear();
+  }
+  if (p.size() > 1 && p.back() == '%') {
+    end = p.find_last_not_of('%') + 1;
+    suffix.clear();
+  }
+  bool prev_bs = false;
+  for (size_t i = start; i < end; ++i) {
+    const char c = p[i];
+    if (c == '_') {
+      out += prev_bs ? "_" : ".";
+    } else if (c == '%') {
+      out += prev_bs ? "%" : ".*";
+    } else {
+      if (prev_bs || (c > 0 && strchr("^$.{}[]()*+?|<>-&/", c))) out += '\\';
+      out += c;
+    }
+    prev_bs = c == '\\';
+  }
+  if (prev_bs) out += '\\';
+  return out + suffix;
+}
+
 std::string filter_to_string(const ph_query* q, int32_t root) {
   const ph_filter_node& f = node_at(q, root);
   auto join = [&](const char* sep) {
@@ -122,6 +153,8 @@ std::string filter_to_string(const ph_query* q, int32_t root) {
     case PH_PRED_NOT_EQ: return lhs + " != '" + (p.num_values > 0 ? lit(p.values[0]) : "") + "'"; // NotEqPredicate :63-65
     case PH_PRED_IN: return list(" IN ");
     case PH_PRED_NOT_IN: return list(" NOT IN ");
+    case PH_PRED_LIKE:  // rewritten to REGEXP_LIKE before planning: RegexpLikePredicate.toString (:72-74)
+      return "regexp_like(" + lhs + ",'" + like_to_regexp(p.num_values > 0 ? lit(p.values[0]) : "") + "')";
     case PH_PRED_RANGE: {  // RangePredicate.toString (:122-134)
       const std::string lo = p.lower ? lit(p.lower) : "*", hi = p.upper ? lit(p.upper) : "*";
       if (lo == "*") return lhs + (p.upper_inclusive ? " <= '" : " < '") + hi + "'";

@@ -28,6 +28,7 @@
 
 #include "pinot_hip.h"
 #include "and_walk.h"
+#include "like_match.h"
 
 namespace ph {
 
@@ -909,6 +910,12 @@ struct RangeSliceLeaf {
   int32_t pad;
 };
 
+// k_like_dict's answer for one (column, pattern): bit i of words[i / 64] = dictId i matches
+struct LikeResult {
+  std::vector<uint64_t> words;
+  int64_t count = 0;
+};
+
 struct Column {
   std::string name;
   int32_t data_type = PH_INT;
@@ -940,12 +947,20 @@ struct Column {
   DeviceBuffer d_fwd;
   DeviceBuffer d_values;
   DeviceBuffer d_inverted;
+  // a STRING column's dictionary as the segment stores it (string_width bytes per entry, zero padded, and padded with
+  // zero entries to whole tiles: like_dict_alloc_bytes), kept in HBM at pin for k_like_dict; the last LIKE pattern's
+  // dictId bitmap is kept (under cache_mu) for the planning passes of one query that evaluate the predicate again
+  DeviceBuffer d_strings;
+  int32_t string_width = 0;
+  struct Context* ctx = nullptr;  // the context the column is pinned on
+  mutable std::string like_pattern;
+  mutable std::shared_ptr<const LikeResult> like_result;
   // a star-tree view's distinctCountHLL__<col> pair (startree.cpp): no forward index or dictionary, but every record's
   // serialized HyperLogLog as sketch_words native-endian RegisterSet words, [num_docs][sketch_words] in HBM
   DeviceBuffer d_sketch;
   int32_t sketch_words = 0;
   int32_t sketch_log2m = 0;
-  std::mutex cache_mu;
+  mutable std::mutex cache_mu;
   std::map<int, HllTable> hll_tables;                                // by log2m
   bool vpacked_ready = false;                                        // VK_PACKED stream built
   std::unique_ptr<DeviceBuffer> d_vpacked;
@@ -1402,6 +1417,16 @@ inline bool is_with_time(int32_t t) { return t == PH_AGG_FIRSTWITHTIME || t == P
 bool has_with_time_aggregation(const ph_query* q);
 void withtime_validate(const ph_query* q);  // host-only argument and shape checks of such a query
 ph_result* withtime_execute(Context* ctx, const ph_query* q, ph_segment* const* segs, int32_t nseg);
+// like_dict.hip: a LIKE pattern compiled for k_like_dict (PH_ERR_UNSUPPORTED past the program's limits), the kernel's
+// launch over a pinned STRING dictionary (bitmap: (card + 63) / 64 words, each written once; *count zeroed by the
+// caller), and the buffer size its tile loads need
+LikeProgram like_compile(const std::string& pattern);
+void launch_like_dict(const uint8_t* dict, int32_t card, int32_t width, const LikeProgram& prog,
+                      unsigned long long* bitmap, unsigned long long* count, int num_cus, hipStream_t s);
+size_t like_dict_alloc_bytes(int64_t card, int32_t width);
+void like_tile_shape(int32_t width, int32_t* tile_entries, int32_t* stride_bytes);
+// the reference's regex text of a LIKE pattern (likeToRegexpLike), for RegexpLikePredicate.toString
+std::string like_to_regexp(const std::string& pattern);
 // FilterContext.toString of the tree rooted at `root` (FilterContext.java:94-114 and each Predicate.toString)
 std::string filter_to_string(const ph_query* q, int32_t root);
 ph_result* query_execute_impl(Context* ctx, const ph_query* q, ph_segment* const* segs, int32_t nseg,

@@ -157,7 +157,68 @@ DictIdSet evaluate_raw_real(const ph_predicate& p, const Column& c) {
   return r;
 }
 
+// LIKE: the reference rewrites it to REGEXP_LIKE, whose dictionary-based evaluator runs the pattern's Matcher.find()
+// over every dictionary value (RegexpLikePredicateEvaluatorFactory.java:55-81).  Here k_like_dict does, over the padded
+// dictionary the pin keeps in HBM, on a lane of the column's context; there is no host evaluator.  One query plans a
+// segment's filter more than once (plan class, index countability, the scan's program): the column keeps the last
+// pattern's answer.
+std::shared_ptr<const LikeResult> like_dict_ids(const ph_predicate& p, const Column& c) {
+  if (c.data_type != PH_STRING)
+    fail(PH_ERR_UNSUPPORTED, "LIKE on the non-STRING column " + c.name + " is not on the GPU path");
+  if (p.num_values != 1 || !p.values || !p.values[0]) fail(PH_ERR_BAD_QUERY, "LIKE predicate needs one pattern");
+  const std::string pat = p.values[0];
+  const LikeProgram prog = like_compile(pat);
+  int32_t tile = 0, stride = 0;
+  like_tile_shape(std::max(1, c.string_width), &tile, &stride);
+  if (!tile)
+    fail(PH_ERR_UNSUPPORTED, "LIKE: dictionary entries of " + std::to_string(c.string_width) + " bytes (column " +
+                                 c.name + ") are wider than the kernel's LDS tile");
+  std::lock_guard<std::mutex> lk(c.cache_mu);
+  if (c.like_result && c.like_pattern == pat) return c.like_result;
+  auto r = std::make_shared<LikeResult>();
+  const int64_t card = c.cardinality;
+  const size_t nwords = (size_t)((card + 63) / 64);
+  r->words.assign(nwords, 0);
+  if (card > 0) {
+    if (!c.ctx || !c.d_strings.ptr) fail(PH_ERR_UNSUPPORTED, "LIKE: column " + c.name + " has no pinned dictionary");
+    PH_HIP_CHECK(hipSetDevice(c.ctx->device));
+    LaneGuard lane(c.ctx);
+    const hipStream_t st = lane.lane->stream;
+    Scratch sc(c.ctx, st);
+    unsigned long long* out = sc.alloc<unsigned long long>(nwords + 1);  // the bitmap, then the counter
+    PH_HIP_CHECK(hipMemsetAsync(out + nwords, 0, sizeof(unsigned long long), st));
+    launch_like_dict(c.d_strings.as<uint8_t>(), (int32_t)card, c.string_width, prog, out, out + nwords,
+                     c.ctx->num_cus, st);
+    std::vector<unsigned long long> host(nwords + 1);
+    PH_HIP_CHECK(hipMemcpyAsync(host.data(), out, sizeof(unsigned long long) * (nwords + 1), hipMemcpyDeviceToHost, st));
+    PH_HIP_CHECK(hipStreamSynchronize(st));
+    std::copy(host.begin(), host.begin() + (ptrdiff_t)nwords, r->words.begin());
+    r->count = (int64_t)host[nwords];
+  }
+  c.like_pattern = pat;
+  c.like_result = r;
+  return r;
+}
+
+DictIdSet evaluate_like(const ph_predicate& p, const Column& c) {
+  const std::shared_ptr<const LikeResult> m = like_dict_ids(p, c);
+  DictIdSet r;
+  const int64_t card = c.cardinality;
+  if (m->count == 0) { r.always_false = true; return r; }
+  if (m->count == card) { r.always_true = true; return r; }
+  r.ids.reserve((size_t)m->count);
+  for (size_t w = 0; w < m->words.size(); ++w)
+    for (uint64_t x = m->words[w]; x; x &= x - 1) r.ids.push_back((int32_t)(64 * w + (size_t)__builtin_ctzll(x)));
+  if (r.ids.back() - r.ids.front() + 1 == (int32_t)r.ids.size()) {
+    r.is_range = true;
+    r.start = r.ids.front();
+    r.end = r.ids.back() + 1;
+  }
+  return r;
+}
+
 DictIdSet evaluate_predicate(const ph_predicate& p, const Column& c) {
+  if (p.type == PH_PRED_LIKE) return evaluate_like(p, c);
   if (c.is_raw && (c.dict.type == PH_FLOAT || c.dict.type == PH_DOUBLE)) return evaluate_raw_real(p, c);
   DictIdSet r;
   const Dictionary& d = c.dict;
@@ -311,14 +372,18 @@ struct Planner {
     if (s.always_false) { n.kind = L_NONE; return n; }
     if (s.always_true) { n.kind = L_ALL; return n; }
     const int sl = slot.at(p.column);
-    if (c.is_sorted) {
+    // REGEXP_LIKE without an FST index is a ScanBasedFilterOperator whatever indexes the column has
+    // (FilterOperatorUtils.java:105-112): a LIKE leaf scans the dictIds (on a sorted column the same docs as the union
+    // of the matching dictIds' ranges), with a scan leaf's place in the AND order and a scan leaf's statistic
+    const bool like = p.type == PH_PRED_LIKE;
+    if (c.is_sorted && !like) {
       n.op = OP_DOCRANGES;
       n.ranges = sorted_doc_ranges(c, s);
       if (n.ranges.empty()) { n.kind = L_NONE; return n; }
       if (n.ranges.size() == 2 && n.ranges[0] == 0 && n.ranges[1] >= seg->num_docs - 1) { n.kind = L_ALL; return n; }
       return n;
     }
-    if (p.type != PH_PRED_RANGE && c.has_inverted()) {
+    if (p.type != PH_PRED_RANGE && !like && c.has_inverted()) {
       // InvertedIndexFilterOperator: OR of the matching bitmaps; exclusive predicates OR the excluded
       // bitmaps and flip (InvertedIndexFilterOperator.java:58-94)
       BitmapLeaf b{seg, &c, {}};
@@ -1104,6 +1169,8 @@ std::shared_ptr<GlobalDict> union_dictionary(const std::string& col, const std::
 }
 
 std::vector<char> predicate_dict_ids(const ph_predicate& p, const Column& c, bool* always_true, bool* always_false) {
+  // (the star-tree planner keeps such a query off the trees: extract_predicates)
+  if (p.type == PH_PRED_LIKE) fail(PH_ERR_UNSUPPORTED, "LIKE in star-tree predicate matching");
   const DictIdSet s = evaluate_predicate(p, c);
   *always_true = s.always_true;
   *always_false = s.always_false;

@@ -494,6 +494,7 @@ ph_segment* segment_pin_impl(Context* ctx, const ph_segment_desc* desc) {
     if (!d.name) fail(PH_ERR_INVALID_ARGUMENT, "column without a name");
     auto col = std::make_unique<Column>();
     col->name = d.name;
+    col->ctx = ctx;
     col->data_type = d.data_type;
     col->cardinality = d.cardinality;
     col->is_sorted = d.is_sorted != 0;
@@ -589,6 +590,14 @@ ph_segment* segment_pin_impl(Context* ctx, const ph_segment_desc* desc) {
       PH_HIP_CHECK(hipMemcpyAsync(col->d_values.ptr, vsrc, sizeof(int64_t) * card, hipMemcpyHostToDevice,
                                   st));
       seg->device_bytes += col->d_values.bytes;
+    } else if (card > 0) {
+      // the padded dictionary itself, for k_like_dict (the LIKE predicate is evaluated on the device only)
+      const size_t used = (size_t)card * (size_t)d.dictionary_entry_size;
+      col->string_width = d.dictionary_entry_size;
+      col->d_strings.alloc(like_dict_alloc_bytes(card, d.dictionary_entry_size), ctx->device);
+      PH_HIP_CHECK(hipMemsetAsync(static_cast<uint8_t*>(col->d_strings.ptr) + used, 0, col->d_strings.bytes - used, st));
+      PH_HIP_CHECK(hipMemcpyAsync(col->d_strings.ptr, d.dictionary, used, hipMemcpyHostToDevice, st));
+      seg->device_bytes += col->d_strings.bytes;
     }
     if (d.inverted_index && d.inverted_index_size) {
       const uint8_t* inv = static_cast<const uint8_t*>(d.inverted_index);

@@ -123,6 +123,48 @@ class RangePredicate(Predicate):
                 f"{c} {'<=' if self.upper_inclusive else '<'} '{self.upper}')")
 
 
+_REGEXP_METACHARACTERS = "^$.{}[]()*+?|<>-&/"
+
+
+def like_to_regexp_like(pattern: str) -> str:
+    """RegexpPatternConverterUtils.likeToRegexpLike (:43-131): the regex a LIKE pattern is rewritten to."""
+    if pattern == "":
+        return "^$"
+    prefix, suffix, body = "^", "$", pattern
+    if pattern[0] == "%":
+        body = pattern.lstrip("%")
+        if body == "":
+            return ""
+        prefix = ""
+    if len(pattern) > 1 and pattern[-1] == "%":
+        body = body.rstrip("%")  # cut without a look at an escape before the run, as the converter does
+        suffix = ""
+    out, prev_bs = [prefix], False
+    for c in body:
+        if c == "_":
+            out.append(c if prev_bs else ".")
+        elif c == "%":
+            out.append(c if prev_bs else ".*")
+        else:
+            if c in _REGEXP_METACHARACTERS or prev_bs:
+                out.append("\\")
+            out.append(c)
+        prev_bs = c == "\\"
+    if prev_bs:
+        out.append("\\")
+    return "".join(out) + suffix
+
+
+@dataclass(frozen=True)
+class LikePredicate(Predicate):
+    """``column LIKE 'pattern'``; the reference rewrites it to REGEXP_LIKE before planning."""
+    pattern: str
+    TYPE = "LIKE"
+
+    def to_string(self) -> str:  # RegexpLikePredicate.java:72-74
+        return f"regexp_like({self.column},'{like_to_regexp_like(self.pattern)}')"
+
+
 # --------------------------------------------------------------------------- filter tree
 @dataclass(frozen=True)
 class FilterContext:
@@ -298,7 +340,7 @@ _TOKEN = re.compile(
     r"|(?P<qid>\"[^\"]*\")|(?P<op><>|!=|<=|>=|=|<|>|\(|\)|\[|\]|,|\*|;|\+|-))")
 
 _KEYWORDS = {"SELECT", "FROM", "WHERE", "GROUP", "BY", "ORDER", "LIMIT", "AND", "OR", "NOT", "IN",
-             "BETWEEN", "AS", "ASC", "DESC", "SET", "TOP"}
+             "BETWEEN", "AS", "ASC", "DESC", "SET", "TOP", "LIKE"}
 
 
 class SqlParseError(ValueError):
@@ -562,8 +604,14 @@ class _Parser:
             hi = self.literal()
             f = FilterContext.pred(RangePredicate(col, lo, hi, True, True))
             return FilterContext.not_(f) if negate else f
+        if self.accept("kw", "LIKE"):
+            t = self.take()
+            if t[0] != "str":
+                raise SqlParseError(f"LIKE needs a string literal pattern, got {t}")
+            f = FilterContext.pred(LikePredicate(col, t[1][1:-1].replace("''", "'")))
+            return FilterContext.not_(f) if negate else f
         if negate:
-            raise SqlParseError("NOT must precede IN/BETWEEN")
+            raise SqlParseError("NOT must precede IN/BETWEEN/LIKE")
         op = self.take()
         if op[0] != "op":
             raise SqlParseError(f"expected comparison, got {op}")
