@@ -135,14 +135,27 @@ typedef struct {
  * `%`, more than 128 bytes, or more than 64 bytes in one run; a pattern that holds a line terminator, or a backslash
  * before a regex metacharacter (where the reference's regex is not the literal); dictionary entries wider than 256
  * bytes.  A query holding a LIKE is not answered from a star-tree: it scans the segment's own docs. */
+/* PH_PRED_REGEXP_LIKE: `REGEXP_LIKE(column, values[0])` (num_values == 1) on a STRING column, the predicate the reference
+ * evaluates itself (RegexpLikePredicate): java.util.regex's find() with CASE_INSENSITIVE | UNICODE_CASE
+ * (RegexpLikePredicate.java:49) on every dictionary value.  The host compiles the pattern to a byte-level DFA and a
+ * kernel walks every entry of the pinned dictionary through it; the leaf, NOT, FILTER(WHERE ...) and the star-tree rule
+ * are PH_PRED_LIKE's.  Accepted: ASCII literals and escaped metacharacters, `.`, `[...]` / `[^...]` of ASCII members,
+ * ranges and \d \w \s \D \W \S, those six outside brackets, `|`, `( )`, `(?: )`, `* + ? {n} {n,} {n,m}` and their
+ * lazy forms, `^`, `$`.  PH_ERR_UNSUPPORTED, each with its own message: a non-STRING column; a non-ASCII character or a
+ * line terminator in the pattern; possessive quantifiers; backreferences; lookaround; \b \B \A \z \Z \G; inline flags;
+ * \p{} and POSIX classes; \u \x \0 \c escapes and \Q..\E; named and atomic groups; nested classes and `&&`; a counted
+ * repetition directly after another quantifier; a pattern that needs more than 1024 NFA nodes, 255 DFA states or 64
+ * byte classes; dictionary entries wider than 256 bytes.  PH_ERR_BAD_QUERY: a pattern java.util.regex rejects
+ * (unbalanced parenthesis, dangling quantifier, unclosed class).  LIKE keeps its own evaluator and answers. */
 typedef enum {
-  PH_PRED_EQ = 0, PH_PRED_NOT_EQ = 1, PH_PRED_IN = 2, PH_PRED_NOT_IN = 3, PH_PRED_RANGE = 4, PH_PRED_LIKE = 5
+  PH_PRED_EQ = 0, PH_PRED_NOT_EQ = 1, PH_PRED_IN = 2, PH_PRED_NOT_IN = 3, PH_PRED_RANGE = 4, PH_PRED_LIKE = 5,
+  PH_PRED_REGEXP_LIKE = 6
 } ph_predicate_type;
 
 typedef struct {
   int32_t type;                 /* ph_predicate_type */
   const char* column;
-  int32_t num_values;           /* EQ / NOT_EQ: 1; IN / NOT_IN: n; LIKE: 1 (the pattern) */
+  int32_t num_values;           /* EQ / NOT_EQ: 1; IN / NOT_IN: n; LIKE / REGEXP_LIKE: 1 (the pattern) */
   const char* const* values;    /* literals as strings, as Pinot's Predicate keeps them */
   const char* lower;            /* RANGE bounds; "*" = RangePredicate.UNBOUNDED */
   const char* upper;

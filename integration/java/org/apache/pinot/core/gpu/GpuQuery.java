@@ -29,7 +29,7 @@ import org.apache.pinot.segment.spi.AggregationFunctionType;
  * null handling, non-identifier group-by expressions, aggregations other than
  * COUNT / SUM / MIN / MAX / DISTINCTCOUNTHLL / DISTINCTCOUNT / PERCENTILE (over a column; SUM / MIN / MAX also over a 2-operand
  * mult/sub/add), predicates other than
- * EQ / NOT_EQ / IN / NOT_IN / RANGE / a rewritten LIKE on identifiers, and a segment group trim (GroupByOperator.java:114-130) ordered
+ * EQ / NOT_EQ / IN / NOT_IN / RANGE / REGEXP_LIKE (a rewritten LIKE, or a regex of the library's subset) on identifiers, and a segment group trim (GroupByOperator.java:114-130) ordered
  * by anything but group-by columns and aggregations.
  */
 public final class GpuQuery {
@@ -284,7 +284,7 @@ public final class GpuQuery {
 
     // The LIKE pattern whose rewrite (RegexpPatternConverterUtils.likeToRegexpLike) is `regex`: `.*` -> %, `.` -> _,
     // an escaped character -> itself (\_ and \% stay escaped); checked by converting the candidate back, so any other
-    // regex is refused and keeps the CPU plan
+    // regex is refused here and travels as a REGEXP_LIKE
     static String likePatternOf(String regex) {
       StringBuilder sb = new StringBuilder();
       int i = 0;
@@ -370,9 +370,16 @@ public final class GpuQuery {
         }
         case REGEXP_LIKE:
           // a LIKE reaches the server rewritten (RequestContextUtils: likeToRegexpLike); the library takes the LIKE
-          // pattern itself, so only a regex that is such a rewrite goes to the GPU
-          type = PinotHipJni.PRED_LIKE;
-          values.add(likePatternOf(((RegexpLikePredicate) p).getValue()));
+          // pattern itself for a regex that is such a rewrite (its answers stay as they were, case-sensitive: the known
+          // divergence recorded in DESIGN.md), and any other regex as PH_PRED_REGEXP_LIKE, which has the reference's
+          // flags; what the library's regex subset refuses comes back as PH_ERR_UNSUPPORTED and keeps the CPU plan
+          try {
+            values.add(likePatternOf(((RegexpLikePredicate) p).getValue()));
+            type = PinotHipJni.PRED_LIKE;
+          } catch (UnsupportedOperationException e) {
+            values.add(((RegexpLikePredicate) p).getValue());
+            type = PinotHipJni.PRED_REGEXP_LIKE;
+          }
           break;
         default:
           throw new UnsupportedOperationException(p.getType().toString());

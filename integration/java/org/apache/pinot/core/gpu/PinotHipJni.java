@@ -21,7 +21,8 @@ public final class PinotHipJni {
       AGG_DISTINCTCOUNT = 5, AGG_PERCENTILE = 6, AGG_SKEWNESS = 13, AGG_KURTOSIS = 14, AGG_HISTOGRAM = 15,
       AGG_FIRSTWITHTIME = 16, AGG_LASTWITHTIME = 17;
   public static final int FILTER_AND = 0, FILTER_OR = 1, FILTER_NOT = 2, FILTER_PREDICATE = 3;
-  public static final int PRED_EQ = 0, PRED_NOT_EQ = 1, PRED_IN = 2, PRED_NOT_IN = 3, PRED_RANGE = 4, PRED_LIKE = 5;
+  public static final int PRED_EQ = 0, PRED_NOT_EQ = 1, PRED_IN = 2, PRED_NOT_IN = 3, PRED_RANGE = 4, PRED_LIKE = 5,
+      PRED_REGEXP_LIKE = 6;
   public static final int EXPR_NONE = 0, EXPR_MULT = 1, EXPR_SUB = 2, EXPR_ADD = 3;
 
   static native long ctxCreate(int device);                                              // ph_ctx_create

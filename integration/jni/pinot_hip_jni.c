@@ -202,7 +202,7 @@ static int decode_query(const jint* desc, jsize nd, const char** strs, jsize ns,
     for (int j = 0; j < b->nodes[i].num_children; ++j) NEXT(b->ints[ki++]);
   }
   for (int i = 0; i < q->num_predicates; ++i) {
-    NEXT(b->preds[i].type); /* ph_predicate_type as is; PH_PRED_LIKE carries its pattern as the one value */
+    NEXT(b->preds[i].type); /* ph_predicate_type as is; PH_PRED_LIKE and PH_PRED_REGEXP_LIKE carry their pattern as the one value */
     NEXT(tmp);
     b->preds[i].column = S(tmp);
     NEXT(b->preds[i].num_values);

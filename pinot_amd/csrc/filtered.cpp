@@ -155,6 +155,8 @@ std::string filter_to_string(const ph_query* q, int32_t root) {
     case PH_PRED_NOT_IN: return list(" NOT IN ");
     case PH_PRED_LIKE:  // rewritten to REGEXP_LIKE before planning: RegexpLikePredicate.toString (:72-74)
       return "regexp_like(" + lhs + ",'" + like_to_regexp(p.num_values > 0 ? lit(p.values[0]) : "") + "')";
+    case PH_PRED_REGEXP_LIKE:  // RegexpLikePredicate.toString (:72-74)
+      return "regexp_like(" + lhs + ",'" + (p.num_values > 0 ? lit(p.values[0]) : "") + "')";
     case PH_PRED_RANGE: {  // RangePredicate.toString (:122-134)
       const std::string lo = p.lower ? lit(p.lower) : "*", hi = p.upper ? lit(p.upper) : "*";
       if (lo == "*") return lhs + (p.upper_inclusive ? " <= '" : " < '") + hi + "'";

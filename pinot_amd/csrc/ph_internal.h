@@ -29,6 +29,7 @@
 #include "pinot_hip.h"
 #include "and_walk.h"
 #include "like_match.h"
+#include "regex_dfa.h"
 
 namespace ph {
 
@@ -910,7 +911,8 @@ struct RangeSliceLeaf {
   int32_t pad;
 };
 
-// k_like_dict's answer for one (column, pattern): bit i of words[i / 64] = dictId i matches
+// k_like_dict's or k_regex_dict's answer for one (column, predicate type, pattern): bit i of words[i / 64] = dictId i
+// matches
 struct LikeResult {
   std::vector<uint64_t> words;
   int64_t count = 0;
@@ -954,6 +956,7 @@ struct Column {
   int32_t string_width = 0;
   struct Context* ctx = nullptr;  // the context the column is pinned on
   mutable std::string like_pattern;
+  mutable int32_t like_type = -1;  // PH_PRED_LIKE or PH_PRED_REGEXP_LIKE: `LIKE 'ab'` and `REGEXP_LIKE(s, 'ab')` differ
   mutable std::shared_ptr<const LikeResult> like_result;
   // a star-tree view's distinctCountHLL__<col> pair (startree.cpp): no forward index or dictionary, but every record's
   // serialized HyperLogLog as sketch_words native-endian RegisterSet words, [num_docs][sketch_words] in HBM
@@ -1425,6 +1428,14 @@ void launch_like_dict(const uint8_t* dict, int32_t card, int32_t width, const Li
                       unsigned long long* bitmap, unsigned long long* count, int num_cus, hipStream_t s);
 size_t like_dict_alloc_bytes(int64_t card, int32_t width);
 void like_tile_shape(int32_t width, int32_t* tile_entries, int32_t* stride_bytes);
+// regex_dfa.cpp: a REGEXP_LIKE pattern compiled to the byte-level DFA k_regex_dict walks (PH_ERR_UNSUPPORTED outside
+// the accepted syntax or past the caps, PH_ERR_BAD_QUERY for what java.util.regex rejects); regex_dict.hip: the kernel's
+// launch over a pinned STRING dictionary (the buffer k_like_dict reads; `prog`: regex_program_bytes of the program, in
+// device memory; bitmap and count as launch_like_dict's)
+RegexProgram regex_compile(const std::string& pattern);
+void launch_regex_dict(const uint8_t* dict, int32_t card, int32_t width, const uint8_t* prog, uint32_t prog_bytes,
+                       unsigned long long* bitmap, unsigned long long* count, int num_cus, hipStream_t s);
+void regex_tile_shape(int32_t width, int32_t* tile_entries, int32_t* stride_bytes);
 // the reference's regex text of a LIKE pattern (likeToRegexpLike), for RegexpLikePredicate.toString
 std::string like_to_regexp(const std::string& pattern);
 // FilterContext.toString of the tree rooted at `root` (FilterContext.java:94-114 and each Predicate.toString)

@@ -162,39 +162,59 @@ DictIdSet evaluate_raw_real(const ph_predicate& p, const Column& c) {
 // dictionary the pin keeps in HBM, on a lane of the column's context; there is no host evaluator.  One query plans a
 // segment's filter more than once (plan class, index countability, the scan's program): the column keeps the last
 // pattern's answer.
+//
+// REGEXP_LIKE itself takes the same road with its own compiler and kernel: regex_compile makes the byte-level DFA
+// (regex_dfa.cpp; the reference's flags, CASE_INSENSITIVE | UNICODE_CASE), the program is uploaded to query scratch
+// (it is too big for kernel arguments) and k_regex_dict walks every entry through it.  The kept answer is keyed on
+// (predicate type, pattern).
 std::shared_ptr<const LikeResult> like_dict_ids(const ph_predicate& p, const Column& c) {
+  const bool regex = p.type == PH_PRED_REGEXP_LIKE;
+  const std::string what = regex ? "REGEXP_LIKE" : "LIKE";
   if (c.data_type != PH_STRING)
-    fail(PH_ERR_UNSUPPORTED, "LIKE on the non-STRING column " + c.name + " is not on the GPU path");
-  if (p.num_values != 1 || !p.values || !p.values[0]) fail(PH_ERR_BAD_QUERY, "LIKE predicate needs one pattern");
+    fail(PH_ERR_UNSUPPORTED, what + " on the non-STRING column " + c.name + " is not on the GPU path");
+  if (p.num_values != 1 || !p.values || !p.values[0]) fail(PH_ERR_BAD_QUERY, what + " predicate needs one pattern");
   const std::string pat = p.values[0];
-  const LikeProgram prog = like_compile(pat);
+  LikeProgram prog{};
+  std::unique_ptr<RegexProgram> dfa;
+  if (regex) dfa = std::make_unique<RegexProgram>(regex_compile(pat));
+  else prog = like_compile(pat);
   int32_t tile = 0, stride = 0;
-  like_tile_shape(std::max(1, c.string_width), &tile, &stride);
+  if (regex) regex_tile_shape(std::max(1, c.string_width), &tile, &stride);
+  else like_tile_shape(std::max(1, c.string_width), &tile, &stride);
   if (!tile)
-    fail(PH_ERR_UNSUPPORTED, "LIKE: dictionary entries of " + std::to_string(c.string_width) + " bytes (column " +
+    fail(PH_ERR_UNSUPPORTED, what + ": dictionary entries of " + std::to_string(c.string_width) + " bytes (column " +
                                  c.name + ") are wider than the kernel's LDS tile");
   std::lock_guard<std::mutex> lk(c.cache_mu);
-  if (c.like_result && c.like_pattern == pat) return c.like_result;
+  if (c.like_result && c.like_type == p.type && c.like_pattern == pat) return c.like_result;
   auto r = std::make_shared<LikeResult>();
   const int64_t card = c.cardinality;
   const size_t nwords = (size_t)((card + 63) / 64);
   r->words.assign(nwords, 0);
   if (card > 0) {
-    if (!c.ctx || !c.d_strings.ptr) fail(PH_ERR_UNSUPPORTED, "LIKE: column " + c.name + " has no pinned dictionary");
+    if (!c.ctx || !c.d_strings.ptr) fail(PH_ERR_UNSUPPORTED, what + ": column " + c.name + " has no pinned dictionary");
     PH_HIP_CHECK(hipSetDevice(c.ctx->device));
     LaneGuard lane(c.ctx);
     const hipStream_t st = lane.lane->stream;
     Scratch sc(c.ctx, st);
     unsigned long long* out = sc.alloc<unsigned long long>(nwords + 1);  // the bitmap, then the counter
     PH_HIP_CHECK(hipMemsetAsync(out + nwords, 0, sizeof(unsigned long long), st));
-    launch_like_dict(c.d_strings.as<uint8_t>(), (int32_t)card, c.string_width, prog, out, out + nwords,
-                     c.ctx->num_cus, st);
+    if (regex) {
+      const uint32_t bytes = regex_program_bytes(*dfa);
+      uint8_t* d_prog = sc.alloc<uint8_t>(bytes);
+      PH_HIP_CHECK(hipMemcpyAsync(d_prog, dfa.get(), bytes, hipMemcpyHostToDevice, st));  // dfa outlives the sync below
+      launch_regex_dict(c.d_strings.as<uint8_t>(), (int32_t)card, c.string_width, d_prog, bytes, out, out + nwords,
+                        c.ctx->num_cus, st);
+    } else {
+      launch_like_dict(c.d_strings.as<uint8_t>(), (int32_t)card, c.string_width, prog, out, out + nwords,
+                       c.ctx->num_cus, st);
+    }
     std::vector<unsigned long long> host(nwords + 1);
     PH_HIP_CHECK(hipMemcpyAsync(host.data(), out, sizeof(unsigned long long) * (nwords + 1), hipMemcpyDeviceToHost, st));
     PH_HIP_CHECK(hipStreamSynchronize(st));
     std::copy(host.begin(), host.begin() + (ptrdiff_t)nwords, r->words.begin());
     r->count = (int64_t)host[nwords];
   }
+  c.like_type = p.type;
   c.like_pattern = pat;
   c.like_result = r;
   return r;
@@ -218,7 +238,7 @@ DictIdSet evaluate_like(const ph_predicate& p, const Column& c) {
 }
 
 DictIdSet evaluate_predicate(const ph_predicate& p, const Column& c) {
-  if (p.type == PH_PRED_LIKE) return evaluate_like(p, c);
+  if (p.type == PH_PRED_LIKE || p.type == PH_PRED_REGEXP_LIKE) return evaluate_like(p, c);
   if (c.is_raw && (c.dict.type == PH_FLOAT || c.dict.type == PH_DOUBLE)) return evaluate_raw_real(p, c);
   DictIdSet r;
   const Dictionary& d = c.dict;
@@ -375,7 +395,7 @@ struct Planner {
     // REGEXP_LIKE without an FST index is a ScanBasedFilterOperator whatever indexes the column has
     // (FilterOperatorUtils.java:105-112): a LIKE leaf scans the dictIds (on a sorted column the same docs as the union
     // of the matching dictIds' ranges), with a scan leaf's place in the AND order and a scan leaf's statistic
-    const bool like = p.type == PH_PRED_LIKE;
+    const bool like = p.type == PH_PRED_LIKE || p.type == PH_PRED_REGEXP_LIKE;
     if (c.is_sorted && !like) {
       n.op = OP_DOCRANGES;
       n.ranges = sorted_doc_ranges(c, s);
@@ -1170,7 +1190,8 @@ std::shared_ptr<GlobalDict> union_dictionary(const std::string& col, const std::
 
 std::vector<char> predicate_dict_ids(const ph_predicate& p, const Column& c, bool* always_true, bool* always_false) {
   // (the star-tree planner keeps such a query off the trees: extract_predicates)
-  if (p.type == PH_PRED_LIKE) fail(PH_ERR_UNSUPPORTED, "LIKE in star-tree predicate matching");
+  if (p.type == PH_PRED_LIKE || p.type == PH_PRED_REGEXP_LIKE)
+    fail(PH_ERR_UNSUPPORTED, "LIKE / REGEXP_LIKE in star-tree predicate matching");
   const DictIdSet s = evaluate_predicate(p, c);
   *always_true = s.always_true;
   *always_false = s.always_false;

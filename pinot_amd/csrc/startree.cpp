@@ -168,8 +168,8 @@ bool extract_predicates(const ph_query* q, ph_segment* seg, std::vector<ColPreds
     auto it = seg->columns.find(p.column);
     if (it == seg->columns.end()) fail(PH_ERR_BAD_QUERY, std::string("Column not found: ") + p.column);
     if (it->second->is_raw) return false;  // "Star-tree does not support non-dictionary encoded dimension" (:260-263)
-    // LIKE is not matched against star-tree dimensions here: the query scans the segment's own docs
-    if (p.type == PH_PRED_LIKE) return false;
+    // LIKE and REGEXP_LIKE are not matched against star-tree dimensions here: the query scans the segment's own docs
+    if (p.type == PH_PRED_LIKE || p.type == PH_PRED_REGEXP_LIKE) return false;
     predicate_dict_ids(p, *it->second, at, af);
     return true;
   };

@@ -32,7 +32,7 @@ _AGG = {COUNT: N.PH_AGG_COUNT, SUM: N.PH_AGG_SUM, MIN: N.PH_AGG_MIN, MAX: N.PH_A
         COVARSAMP: N.PH_AGG_COVARSAMP, SKEWNESS: N.PH_AGG_SKEWNESS, KURTOSIS: N.PH_AGG_KURTOSIS,
         HISTOGRAM: N.PH_AGG_HISTOGRAM, FIRSTWITHTIME: N.PH_AGG_FIRSTWITHTIME, LASTWITHTIME: N.PH_AGG_LASTWITHTIME}
 _PRED = {"EQ": N.PH_PRED_EQ, "NOT_EQ": N.PH_PRED_NOT_EQ, "IN": N.PH_PRED_IN, "NOT_IN": N.PH_PRED_NOT_IN,
-         "RANGE": N.PH_PRED_RANGE, "LIKE": N.PH_PRED_LIKE}
+         "RANGE": N.PH_PRED_RANGE, "LIKE": N.PH_PRED_LIKE, "REGEXP_LIKE": N.PH_PRED_REGEXP_LIKE}
 
 
 @dataclass
@@ -191,7 +191,7 @@ class _QueryStruct:
                     vals = [p.value]
                 elif p.TYPE in ("IN", "NOT_IN"):
                     vals = list(p.values)
-                elif p.TYPE == "LIKE":
+                elif p.TYPE in ("LIKE", "REGEXP_LIKE"):
                     vals = [p.pattern]
                 else:
                     ps.lower = s(p.lower)

@@ -22,7 +22,7 @@ PH_ERR_CANCELLED = 6
 PH_INT, PH_LONG, PH_FLOAT, PH_DOUBLE, PH_STRING = range(5)
 DATA_TYPES = {"INT": PH_INT, "LONG": PH_LONG, "FLOAT": PH_FLOAT, "DOUBLE": PH_DOUBLE, "STRING": PH_STRING}
 
-PH_PRED_EQ, PH_PRED_NOT_EQ, PH_PRED_IN, PH_PRED_NOT_IN, PH_PRED_RANGE, PH_PRED_LIKE = range(6)
+PH_PRED_EQ, PH_PRED_NOT_EQ, PH_PRED_IN, PH_PRED_NOT_IN, PH_PRED_RANGE, PH_PRED_LIKE, PH_PRED_REGEXP_LIKE = range(7)
 PH_FILTER_AND, PH_FILTER_OR, PH_FILTER_NOT, PH_FILTER_PREDICATE = range(4)
 (PH_AGG_COUNT, PH_AGG_SUM, PH_AGG_MIN, PH_AGG_MAX, PH_AGG_DISTINCTCOUNTHLL, PH_AGG_DISTINCTCOUNT,
  PH_AGG_PERCENTILE, PH_AGG_VARPOP, PH_AGG_VARSAMP, PH_AGG_STDDEVPOP, PH_AGG_STDDEVSAMP, PH_AGG_COVARPOP,

@@ -165,6 +165,16 @@ class LikePredicate(Predicate):
         return f"regexp_like({self.column},'{like_to_regexp_like(self.pattern)}')"
 
 
+@dataclass(frozen=True)
+class RegexpLikePredicate(Predicate):
+    """``REGEXP_LIKE(column, 'pattern')``: java.util.regex's find(), CASE_INSENSITIVE | UNICODE_CASE."""
+    pattern: str
+    TYPE = "REGEXP_LIKE"
+
+    def to_string(self) -> str:  # RegexpLikePredicate.java:72-74
+        return f"regexp_like({self.column},'{self.pattern}')"
+
+
 # --------------------------------------------------------------------------- filter tree
 @dataclass(frozen=True)
 class FilterContext:
@@ -588,6 +598,15 @@ class _Parser:
         return self.predicate()
 
     def predicate(self) -> FilterContext:
+        if self.peek()[0] == "id" and self.peek()[1].upper() == "REGEXP_LIKE" and self.peek(1) == ("op", "("):
+            self.i += 2
+            col = self.ident()
+            self.expect("op", ",")
+            t = self.take()
+            if t[0] != "str":
+                raise SqlParseError(f"REGEXP_LIKE needs a string literal pattern, got {t}")
+            self.expect("op", ")")
+            return FilterContext.pred(RegexpLikePredicate(col, t[1][1:-1].replace("''", "'")))
         col = self.ident()
         negate = bool(self.accept("kw", "NOT"))
         if self.accept("kw", "IN"):
